@@ -23,6 +23,12 @@ with random-init weights; the reference publishes no quantitative numbers
 
 The driver launches N>1 via torch.distributed.run, one rank per GPU; we read
 RANK/LOCAL_RANK/WORLD_SIZE from the env (RCCL over xGMI).
+
+A plain run sets up, warms up, times --steps steps and prints the result
+line. --full additionally probes the serialized per-trigger latency
+(p50_trigger_latency_ms; null without it). --dump-outputs DIR writes what
+the last timed step returned as DIR/<name>.npy (inputs are seeded, so two
+builds can be compared output for output).
 """
 
 from __future__ import annotations
@@ -44,7 +50,36 @@ def _sync():
         torch.cuda.synchronize()
 
 
-def run_steps(step_fn, steps, warmup, dist, device, min_warm_s=None):
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy (float32, or float64 where
+    the tensor already is), at most DUMP_BUDGET_BYTES in all: an array over
+    its share of the budget is reduced to a fixed, seeded sample of its
+    flattened elements (same indices on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64
+                 else torch.float32)
+        host[name] = t.contiguous().numpy()
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BUDGET_BYTES:
+            share = int(DUMP_BUDGET_BYTES * (a.nbytes / total))
+            keep = max(1, share // a.itemsize)
+            if keep < a.size:
+                rng = np.random.default_rng(20240613)
+                idx = np.sort(rng.integers(0, a.size, size=keep))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
+def run_steps(step_fn, steps, warmup, dist, device, min_warm_s=None,
+              extra_quantum=1):
     if min_warm_s is None:
         # TSKD_BENCH_MINWARM=0 disables the extension (rocprof runs: the
         # extra ~3k dispatches overflow the tracer)
@@ -69,6 +104,9 @@ def run_steps(step_fn, steps, warmup, dist, device, min_warm_s=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         n_extra = int(t.item())
     n_extra = min(n_extra, 100_000)
+    # extra_quantum > 1: round the wall-clock-paced count up to a multiple,
+    # for step functions whose state is periodic in the step count
+    n_extra = -(-n_extra // extra_quantum) * extra_quantum
     for _ in range(n_extra):
         step_fn()
     _sync()
@@ -116,6 +154,13 @@ def main() -> None:
                    help="hipGraph-capture the model forward (pipeline mode)")
     p.add_argument("--no-graph", dest="graph", action="store_false")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements beyond the headline "
+                        "figure: [pipeline] the serialized per-trigger "
+                        "latency probe (p50_trigger_latency_ms)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the arrays the last "
+                        "timed step returned as DIR/<name>.npy")
     args = p.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -142,6 +187,9 @@ def main() -> None:
     model = build_model(args.variant).eval()
     eng = MyCNNEngine(model, device=device)
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    last = {}  # what the most recent step returned to its caller
+    min_warm_s = None
+    extra_quantum = 1
 
     if args.mode == "train":
         from tskd_amd.train.hip_trainer import MyCNNHipTrainer
@@ -153,7 +201,12 @@ def main() -> None:
         y = (torch.rand(S, B, device=device) < 0.3).float()
 
         def step():
-            tr.step(x, age, y)
+            last["loss"] = tr.step(x, age, y)
+
+        if args.dump_outputs:
+            # every step updates the weights: keep the step count a function
+            # of the arguments alone (no wall-clock-paced warmup extension)
+            min_warm_s = 0.0
 
         windows_per_step = S * B
         cfg = {"model": args.variant, "global_batch": windows_per_step * world,
@@ -176,7 +229,7 @@ def main() -> None:
         age = torch.full((S, B), 65.0, device=device)
 
         def step():
-            eng.forward(x, age, apply_sigmoid=True)
+            last["probs"] = eng.forward(x, age, apply_sigmoid=True)
 
         windows_per_step = S * B
         cfg = {"model": args.variant, "global_batch": windows_per_step * world,
@@ -189,6 +242,14 @@ def main() -> None:
         se = StreamEngine(S, 10, ring_grid=2048, fs=fs, device=device)
         chan_map = list(range(8))  # 8 active channels
         trigger_samples = int(fs * 60)  # one 60-s trigger per step
+        if args.dump_outputs:
+            # the rings' position repeats every G / gcd(G, NB) triggers and
+            # the window sums are grouped by ring position (last-bit
+            # differences): keep the last step's position a function of the
+            # arguments alone, whatever the warmup extension comes to
+            import math
+            nb = trigger_samples // se.bucket_len
+            extra_quantum = se.G // math.gcd(se.G, nb)
         # Pre-generate one trigger's worth of raw data (synthetic; in
         # production this arrives from the bus).
         raw = torch.randn(S, 8, trigger_samples, device=device, dtype=dtype)
@@ -221,8 +282,9 @@ def main() -> None:
         # per-step wall time is the completion INTERVAL, not the latency of
         # one trigger. Probe the true per-trigger latency (ingest -> model,
         # serialized by a sync after every replay) before the timed loop.
+        # (--full only: not part of the headline figure.)
         trigger_latency_ms = None
-        if tg is not None:
+        if tg is not None and args.full:
             lp = []
             for _ in range(20):
                 _sync()
@@ -239,6 +301,7 @@ def main() -> None:
                 se.ingest_dense(raw, chan_map=chan_map)
                 w = se.windows(batch=1, stride=12, dtype=dtype)
                 probs = eng.forward(w, age, apply_sigmoid=True)
+            last["probs"] = probs
             if dist:
                 if dist.get_backend() == "nccl":
                     # predictions to every rank (RCCL all-gather over xGMI)
@@ -257,10 +320,19 @@ def main() -> None:
 
     if args.mode != "pipeline":
         trigger_latency_ms = None
-    elapsed_s, lat = run_steps(step, args.steps, args.warmup, dist, device)
+    elapsed_s, lat = run_steps(step, args.steps, args.warmup, dist, device,
+                               min_warm_s=min_warm_s,
+                               extra_quantum=extra_quantum)
     total_windows = windows_per_step * args.steps * world
     value = total_windows / elapsed_s
     ms_per_step = elapsed_s / args.steps * 1000.0
+
+    if args.dump_outputs and rank == 0:
+        _sync()
+        outs = dict(last)
+        if args.mode == "train":
+            outs["weights"] = tr.wpack  # the updated packed parameters
+        dump_outputs(args.dump_outputs, outs)
 
     if rank == 0:
         print(json.dumps({

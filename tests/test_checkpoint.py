@@ -83,7 +83,7 @@ class TestFormat:
 
 
 class TestReferenceCheckpoints:
-    """Loads the real upstream .pth files when /root/reference is mounted."""
+    """Loads the real upstream .pth files (tests/golden/reference/model)."""
 
     EXPECT = {
         "MyCNN2.pth": ("MyCNN2", 5240, (4, 7, 5)),
@@ -139,13 +139,14 @@ class TestGoldenWindow:
 
     def test_golden_window_score_stable(self):
         import numpy as np
-        x = np.loadtxt("tests/data/x_testinput.csv", delimiter=",")
+        data = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
+        x = np.loadtxt(os.path.join(data, "x_testinput.csv"), delimiter=",")
         assert x.shape == (120, 10)
-        m = load_checkpoint("tests/data/ref_mycnn5.pth")
+        m = load_checkpoint(os.path.join(data, "ref_mycnn5.pth"))
         with torch.no_grad():
             xt = torch.from_numpy(x.T[None]).float()
             y = torch.sigmoid(m(xt, torch.full((1,), 65.0)))
-        golden = float(open("tests/data/x_testinput.golden").read())
+        golden = float(open(os.path.join(data, "x_testinput.golden")).read())
         assert abs(float(y[0]) - golden) < 1e-6
 
 

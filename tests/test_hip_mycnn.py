@@ -131,9 +131,8 @@ class TestHipForward:
 
     def test_reference_checkpoint_on_gpu(self):
         import os
-        path = "/root/repo/tests/data/ref_mycnn5.pth"
-        if not os.path.exists(path):
-            pytest.skip("golden checkpoint not present")
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                            "data", "ref_mycnn5.pth")
         from tskd_amd.models import load_checkpoint
         m = load_checkpoint(path)
         eng = MyCNNEngine(m, device="cuda")

@@ -222,6 +222,54 @@ class TestBenchWarmupAgreement:
         assert int(c0) > 5       # warmup actually extended past W=2
 
 
+class TestBenchDump:
+    def _bench(self):
+        sys.path.insert(0, REPO)
+        import bench
+        return bench
+
+    def test_dump_outputs_float32_npy(self, tmp_path):
+        import numpy as np
+        bench = self._bench()
+        out = str(tmp_path / "dump")
+        bench.dump_outputs(out, {
+            "probs": torch.arange(6, dtype=torch.bfloat16).reshape(3, 2),
+            "loss": 0.25})
+        probs = np.load(os.path.join(out, "probs.npy"))
+        assert probs.dtype == np.float32 and probs.shape == (3, 2)
+        np.testing.assert_array_equal(probs.ravel(), np.arange(6))
+        assert np.load(os.path.join(out, "loss.npy")).dtype == np.float32
+
+    def test_dump_outputs_budget_sample_is_fixed(self, tmp_path, monkeypatch):
+        import numpy as np
+        bench = self._bench()
+        monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+        big = torch.arange(10_000, dtype=torch.float32)
+        small = torch.ones(24)
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+        a = np.load(tmp_path / "a" / "big.npy")
+        b = np.load(tmp_path / "b" / "big.npy")
+        s = np.load(tmp_path / "a" / "small.npy")
+        assert a.nbytes + s.nbytes <= 4096 and 0 < a.size < 10_000
+        np.testing.assert_array_equal(a, b)      # same indices every run
+        assert (np.diff(a) >= 0).all()           # a sample of the original
+
+    def test_warmup_extension_quantum(self):
+        bench = self._bench()
+        calls = [0]
+
+        def step():
+            calls[0] += 1
+
+        _, lat = bench.run_steps(step, steps=3, warmup=2, dist=None,
+                                 device="cpu", min_warm_s=0.01,
+                                 extra_quantum=512)
+        assert len(lat) == 3
+        extra = calls[0] - 3 - 2
+        assert extra > 0 and extra % 512 == 0
+
+
 class TestSignalSurvey:
     def test_survey_committed_record(self, capsys):
         """Signal-availability survey (explore_fantasia analog) over the

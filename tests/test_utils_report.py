@@ -111,10 +111,12 @@ class TestCsvDemo:
 class TestScriptsImportable:
     def test_scripts_parse(self):
         """The operational scripts must at least import/compile on CPU."""
+        import os
         import py_compile
+        repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         for f in ("scripts/ab_bench.py", "scripts/gpu_soak.py",
                   "scripts/demo_e2e.py"):
-            py_compile.compile(f, doraise=True)
+            py_compile.compile(os.path.join(repo, f), doraise=True)
 
 
 class TestAuxCLIs:
