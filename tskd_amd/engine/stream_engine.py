@@ -521,6 +521,18 @@ class StreamEngine:
                 out.copy_(((out.float() - m) / sd.clamp_min(zeps)).to(dtype))
         return out
 
+    def score_latest(self, model_engine, age: Optional[torch.Tensor] = None,
+                     apply_sigmoid: bool = True) -> torch.Tensor:
+        """(S, 1) scores of every stream's latest model window, computed by
+        the fused serving-tail kernel straight from the ``proc`` ring (no
+        window tensor is materialised). Same result as ``windows(batch=1,
+        dtype=bf16, timelast=True)`` + ``model_engine.forward``; capture-
+        safe (ring position from the device state block when one is set)."""
+        assert self._gpu and self.model_win == 120
+        return model_engine.score_ring(
+            self.proc, self.G, self.nproc, self._dstate_ptr(),
+            self._dstate_gather_extra, age, apply_sigmoid)
+
     @property
     def ready(self) -> bool:
         """A full model window exists (>= 600 s + 180 s of data SINCE THE
@@ -548,6 +560,13 @@ class TriggerGraph:
     read, so one replay per 60-s trigger advances the rings with ZERO host
     work besides the replay call. Requires steady state (every trigger
     produces exactly NB new grid points) and a stable channel map.
+
+    Fused tail (default; ``TSKD_FUSED_TAIL=0`` at capture time turns it
+    off): when the model graph's input is a bf16 timelast buffer with one
+    window per stream and the variant supports it (even channel count equal
+    to the engine's: MyCNN5, MyCNN4), gather -> conv -> LSTM/head collapse
+    into ONE kernel that reads the ``proc`` ring (``score_latest``). In
+    that mode ``graphed_forward.x`` is NOT written; only ``.age`` is read.
     """
 
     def __init__(self, engine: "StreamEngine", raw: torch.Tensor,
@@ -564,6 +583,13 @@ class TriggerGraph:
         self.stride = stride
         self.chan_map = list(chan_map)
         self.overlap = overlap
+        gf = graphed_forward
+        self.fused_tail = (
+            os.environ.get("TSKD_FUSED_TAIL", "1") != "0"
+            and gf.x.dtype == torch.bfloat16
+            and getattr(gf, "timelast", False) and gf.x.shape[1] == 1
+            and engine.model_win == 120
+            and gf.engine.supports_fused_tail(engine.C))
         dev = engine.device
         self.dstate = torch.tensor([engine.head, engine.nproc],
                                    dtype=torch.int64, device=dev)
@@ -579,11 +605,7 @@ class TriggerGraph:
             try:
                 engine.ingest_dense_graph_body(self.raw, self.chan_map,
                                                self.nb)
-                engine.windows(batch=1, stride=stride, dtype=self.gf.x.dtype,
-                               out=self.gf.x,
-                               timelast=getattr(self.gf, "timelast", False))
-                out = self.gf.engine.forward(self.gf.x, self.gf.age,
-                                             apply_sigmoid=True)
+                out = self._score()
                 rc = lib.tskd_preproc_advance_state(
                     ctypes.c_void_p(self.dstate.data_ptr()), self.nb,
                     self.nb, _sptr())
@@ -605,6 +627,18 @@ class TriggerGraph:
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self.out = trigger_body()
+
+    def _score(self) -> torch.Tensor:
+        """Latest-window scores inside a trigger body (after the fill):
+        the fused tail kernel, or gather into gf.x + conv + LSTM/head."""
+        gf = self.gf
+        if self.fused_tail:
+            return self.engine.score_latest(gf.engine, gf.age,
+                                            apply_sigmoid=True)
+        self.engine.windows(batch=1, stride=self.stride, dtype=gf.x.dtype,
+                            out=gf.x,
+                            timelast=getattr(gf, "timelast", False))
+        return gf.engine.forward(gf.x, gf.age, apply_sigmoid=True)
 
     def _init_overlap(self) -> None:
         """Two-stream software-pipelined trigger: ingest(T+1) overlaps the
@@ -641,11 +675,7 @@ class TriggerGraph:
             engine._dstate_gather_extra = nb
             try:
                 engine.fill_graph_kernel(nb)
-                engine.windows(batch=1, stride=self.stride,
-                               dtype=self.gf.x.dtype, out=self.gf.x,
-                               timelast=getattr(self.gf, "timelast", False))
-                out = self.gf.engine.forward(self.gf.x, self.gf.age,
-                                             apply_sigmoid=True)
+                out = self._score()
                 rc = lib.tskd_preproc_advance_state(
                     ctypes.c_void_p(self.dstate.data_ptr()), 0, nb, _sptr())
                 if rc != 0:

@@ -50,6 +50,13 @@ def _load_lib() -> ctypes.CDLL:
         ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
         ctypes.c_int, ctypes.c_void_p,
     ]
+    lib.tskd_serve_tail_fwd.restype = ctypes.c_int
+    lib.tskd_serve_tail_fwd.argtypes = [
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+        ctypes.c_long, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+    ]
     lib.tskd_pack_size.restype = ctypes.c_int
     lib.tskd_pack_size.argtypes = [ctypes.c_int]
     lib.tskd_feat_len.restype = ctypes.c_int
@@ -183,6 +190,47 @@ class MyCNNEngine:
             _stream_ptr())
         if rc != 0:
             raise RuntimeError(f"tskd_lstm_head_fwd failed: hipError {rc}")
+        return out
+
+    def supports_fused_tail(self, n_channels: int) -> bool:
+        """True when :meth:`score_ring` applies: a GPU engine whose model
+        has an even channel count equal to the ring's (MyCNN5, MyCNN4)."""
+        return (self.device.type == "cuda" and self.cin % 2 == 0
+                and self.cin == int(n_channels))
+
+    def score_ring(self, proc: torch.Tensor, G: int, end: int,
+                   dstate_ptr=None, end_extra: int = 0,
+                   age: Optional[torch.Tensor] = None,
+                   apply_sigmoid: bool = False) -> torch.Tensor:
+        """Score the latest window of every stream straight from a
+        StreamEngine's (S, C, G) fp32 ``proc`` ring: window gather + conv +
+        one LSTM step + head in ONE kernel (B = 1, N = 1). The window ends
+        at ``end`` (or at ``dstate[1] + end_extra`` when ``dstate_ptr`` is a
+        device int64[2] state block, as in the window gather). Returns
+        (S, 1) fp32; equals ``windows(batch=1, bf16, timelast)`` followed by
+        :meth:`forward`. Raises for variants the kernel does not cover."""
+        assert proc.dim() == 3 and proc.dtype == torch.float32 \
+            and proc.is_contiguous() and proc.shape[2] == G
+        s, c = proc.shape[0], proc.shape[1]
+        lib = _load_lib()
+        out = torch.empty(s, 1, dtype=torch.float32, device=proc.device)
+        age_ptr = ctypes.c_void_p(0)
+        if age is not None:
+            if age.dtype != torch.float32 or age.shape != (s, 1) \
+                    or not age.is_contiguous():
+                age = age.to(torch.float32).expand(s, 1).contiguous()
+            age_ptr = ctypes.c_void_p(age.data_ptr())
+        rc = lib.tskd_serve_tail_fwd(
+            ctypes.c_void_p(proc.data_ptr()), s, c, int(G),
+            ctypes.c_long(int(end)),
+            dstate_ptr if dstate_ptr is not None else ctypes.c_void_p(0),
+            int(end_extra), age_ptr, ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(self.wpack.data_ptr()),
+            ctypes.c_void_p(self.bfrag.data_ptr()),
+            ctypes.c_float(self.age_eps), int(apply_sigmoid), self.variant,
+            _stream_ptr())
+        if rc != 0:
+            raise RuntimeError(f"tskd_serve_tail_fwd failed: code {rc}")
         return out
 
     def forward(self, x: torch.Tensor, age: Optional[torch.Tensor] = None,

@@ -684,6 +684,253 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_head_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Kernel 3 (serving tail, B = 1, N = 1): window gather + conv stack + ONE
+// LSTM step + head in one kernel, straight from the StreamEngine's fp32
+// `proc` ring. Replaces window_gather_tlast2 -> conv_stack_mfma_tlast ->
+// lstm_head for the one-window-per-stream trigger: the bf16 (120, C) window
+// and the (S, LIN) feature tensor never touch global memory.
+//
+// Schedule = kernel 1c's: one wave per TWO streams, grid-stride. Per pair:
+//   stage   lanes take consecutive t (coalesced per channel row of the
+//           ring), RNE f32->bf16, two channels packed per dword store into
+//           the per-wave time-major image xt[t*CIN + c] (row stride CIN/2
+//           = 5 dwords: conflict-free). The window starts at
+//           (end - 120) mod ring and wraps at most once.
+//   conv1   kernel 1b's even-CIN MFMA im2col loop, A-fragments from LDS,
+//           the pair's chains interleaved, one c1 row set per window.
+//   tail    conv_tail<G, true> unchanged, its feature row pointed at LDS.
+//           The pair shares one p1/c2/feature scratch, and that scratch
+//           lives in window a's image, dead after the MFMA loop: 35.7 KB
+//           of LDS per workgroup (MyCNN5) keeps 4 workgroups per CU. Every
+//           hand-over between the image's two uses crosses a wave_sync().
+//   lstm    lstm_head_kernel's lane layout and operation order for a single
+//           step from h0 = c0 = 0: the whh FMAs and the f*c term are exact
+//           zeros there and are omitted (whh1/whh2 are never loaded); every
+//           kept term keeps its order, so results match the unfused chain.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ unsigned int f32_to_bf16_rne(float f) {
+    // same rounding as f32_to_bf16_ in preprocess_kernels.hip
+    union { float f; unsigned int i; } u;
+    u.f = f;
+    const unsigned int r = u.i + 0x7fffu + ((u.i >> 16) & 1);
+    return r >> 16;
+}
+
+template <class G>
+__global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_kernel(
+    const float* __restrict__ proc,   // (S, CIN, ring) fp32 processed ring
+    const float* __restrict__ age,    // (S) or nullptr
+    float* __restrict__ out,          // (S)
+    const float* __restrict__ wpack,
+    const unsigned short* __restrict__ bfrag,  // [KSTEPS][64][8] bf16 bits
+    int S, int ring, long end_in, const long long* __restrict__ dstate,
+    int end_extra, float age_eps, int apply_sigmoid)
+{
+    static_assert(G::CIN % 2 == 0, "packed staging needs an even CIN");
+    static_assert(G::XTSZ % 8 == 0 && G::XTN % 2 == 0, "");
+    constexpr int NW  = 4 * G::CIN * G::K1 + 4 + 20 + 1;
+    constexpr int LIN = G::LIN;
+    constexpr int CD  = G::CIN / 2;    // dwords per time-major row
+    constexpr int XTD = G::XTSZ / 2;   // padded image, dwords
+    __shared__ float lds_w[NW];
+    __shared__ unsigned int lds_xt[WG_WAVES][2][XTD];
+    __shared__ float lds_c1[WG_WAVES][2][4 * G::C1];
+    // pool/conv2 scratch and the feature row live in window a's image, which
+    // is dead once the MFMA loop has read it (and is restaged every pair)
+    static_assert(4 * G::P1 + G::C2 + LIN <= G::XTN / 2, "scratch > image");
+
+    for (int i = threadIdx.x; i < NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    __syncthreads();
+
+    // wave index is uniform: say so, so ring rows and LDS bases are scalar
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const int unit = lane & 15;
+    const float* b1 = lds_w + G::OB1;
+    unsigned int* xta = lds_xt[wave][0];
+    unsigned int* xtb = lds_xt[wave][1];
+    float* c1a = lds_c1[wave][0];
+    float* c1b = lds_c1[wave][1];
+    float* p1w = (float*)xta;
+    float* c2w = p1w + 4 * G::P1;
+    float* fw = c2w + G::C2;
+
+    bf16x8 bfr[G::KSTEPS];
+    union BU { unsigned int d[4]; unsigned short u[8]; bf16x8 v; };
+    #pragma unroll
+    for (int st = 0; st < G::KSTEPS; ++st) {
+        BU bu;
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+            bu.d[q] = ((const unsigned int*)bfrag)[(st * WAVE + lane) * 4 + q];
+        bfr[st] = bu.v;
+    }
+    // LSTM / head rows (lane = gate row), once per wave. No whh blocks.
+    float wih1[LIN], wih2[16], outw[16];
+    const float bl1 = wpack[G::OBL1 + lane];
+    const float bl2 = wpack[G::OBL2 + lane];
+    #pragma unroll
+    for (int i = 0; i < LIN; ++i) wih1[i] = wpack[G::OWIH1 + lane * LIN + i];
+    #pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        wih2[i] = wpack[G::OWIH2 + lane * 16 + i];
+        outw[i] = wpack[G::OOUTW + i];   // uniform address
+    }
+    const float outb = wpack[G::OOUTB];
+    const bool is_cell_gate = (lane >= 32 && lane < 48);
+
+    // Ring position of the window (uniform): a short ring gives the all-
+    // zero window, like the gather's `ok` predicate at B = 1.
+    const long end = dstate ? (long)dstate[1] + end_extra : end_in;
+    const bool full = end >= G::L;
+    const int start = full ? (int)((end - G::L) % ring) : 0;
+
+    // The A-fragment overread past t = L-1 lands in this zeroed tail of the
+    // wave's own image; staging never writes it, so zero it once.
+    for (int i = G::XTN / 2 + lane; i < XTD; i += WAVE) xta[i] = xtb[i] = 0u;
+
+    // Per-lane byte offsets into a channel row for t = lane + 64*h.
+    constexpr int NT = (G::L + WAVE - 1) / WAVE;
+    unsigned int goff[NT];
+    #pragma unroll
+    for (int h = 0; h < NT; ++h) {
+        unsigned int gi = start + lane + h * WAVE;
+        if (gi >= (unsigned int)ring) gi -= ring;   // at most one wrap
+        goff[h] = gi * 4u;
+    }
+
+    auto stage = [&](unsigned int* xt, long s, bool live) {
+        // uniform row base + 32-bit lane offset; all loads issued first
+        const char* pr = (const char*)(proc + s * ((long)G::CIN * ring));
+        float v[NT][G::CIN];
+        #pragma unroll
+        for (int h = 0; h < NT; ++h) {
+            #pragma unroll
+            for (int c = 0; c < G::CIN; ++c) v[h][c] = 0.f;
+        }
+        if (live) {
+            #pragma unroll
+            for (int h = 0; h < NT; ++h) {
+                if (lane + h * WAVE < G::L) {
+                    #pragma unroll
+                    for (int c = 0; c < G::CIN; ++c)
+                        v[h][c] = *(const float*)(pr + (long)c * ring * 4
+                                                  + goff[h]);
+                }
+            }
+        }
+        #pragma unroll
+        for (int h = 0; h < NT; ++h) {
+            if (lane + h * WAVE < G::L) {
+                #pragma unroll
+                for (int c = 0; c < G::CIN; c += 2)
+                    xt[(lane + h * WAVE) * CD + (c >> 1)] =
+                        f32_to_bf16_rne(v[h][c]) |
+                        (f32_to_bf16_rne(v[h][c + 1]) << 16);
+            }
+        }
+    };
+
+    auto c1_store = [&](float* c1w, const f32x4& acc, int mt) {
+        const int c = lane & 15;
+        if (c < 4) {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = mt * 16 + (lane >> 4) * 4 + r;
+                if (row < G::C1) c1w[c * G::C1 + row] = acc[r] + b1[c];
+            }
+        }
+    };
+
+    // One LSTM step from zero state + head for stream s (feature row in fw).
+    auto lstm_step = [&](long s) {
+        float h1v[16], h2v[16];
+        float ga = bl1, gb = 0.f;
+        #pragma unroll
+        for (int i = 0; i < LIN; i += 2) {
+            ga = fmaf(wih1[i], fw[i], ga);
+            if (i + 1 < LIN) gb = fmaf(wih1[i + 1], fw[i + 1], gb);
+        }
+        float g = ga + gb;
+        float a = is_cell_gate ? tanhf_(g) : sigmoidf_(g);
+        {
+            const float iu = __shfl(a, unit);
+            const float gu = __shfl(a, unit + 32);
+            const float ou = __shfl(a, unit + 48);
+            const float h = ou * tanhf_(iu * gu);
+            #pragma unroll
+            for (int u = 0; u < 16; ++u) h1v[u] = __shfl(h, u);
+        }
+        ga = bl2; gb = 0.f;
+        #pragma unroll
+        for (int u = 0; u < 16; u += 2) {
+            ga = fmaf(wih2[u], h1v[u], ga);
+            gb = fmaf(wih2[u + 1], h1v[u + 1], gb);
+        }
+        g = ga + gb;
+        a = is_cell_gate ? tanhf_(g) : sigmoidf_(g);
+        {
+            const float iu = __shfl(a, unit);
+            const float gu = __shfl(a, unit + 32);
+            const float ou = __shfl(a, unit + 48);
+            const float h = ou * tanhf_(iu * gu);
+            #pragma unroll
+            for (int u = 0; u < 16; ++u) h2v[u] = __shfl(h, u);
+        }
+        if (lane == 0) {
+            float y = outb;
+            #pragma unroll
+            for (int u = 0; u < 16; ++u) y = fmaf(outw[u], h2v[u], y);
+            const float ag = age ? age[s] : 0.f;
+            y *= fmaxf(fmaf(ag, age_eps, 1.0f), 0.0f);
+            if (apply_sigmoid) y = sigmoidf_(y);
+            out[s] = y;
+        }
+        wave_sync();  // feature-row reads done before the next tail's store
+    };
+
+    for (long win = (blockIdx.x * WG_WAVES + wave) * 2; win < S;
+         win += (long)gridDim.x * WG_WAVES * 2) {
+        const long win1 = win + 1;
+        const bool has1 = win1 < S;
+        stage(xta, win, full);
+        stage(xtb, has1 ? win1 : win, full && has1);
+        wave_sync();
+
+        #pragma unroll 1
+        for (int mt = 0; mt < G::MTILES; ++mt) {
+            f32x4 acca = {0.f, 0.f, 0.f, 0.f};
+            f32x4 accb = {0.f, 0.f, 0.f, 0.f};
+            #pragma unroll
+            for (int st = 0; st < G::KSTEPS; ++st) {
+                // even element offset: aligned dwords are fragment dwords
+                const int bd = ((mt * 16 + (lane & 15)) * G::CIN + st * 32
+                                + (lane >> 4) * 8) / 2;
+                BU aa, ab;
+                #pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    aa.d[q] = xta[bd + q];
+                    ab.d[q] = xtb[bd + q];
+                }
+                acca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    aa.v, bfr[st], acca, 0, 0, 0);
+                accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    ab.v, bfr[st], accb, 0, 0, 0);
+            }
+            c1_store(c1a, acca, mt);
+            c1_store(c1b, accb, mt);
+        }
+        wave_sync();  // both images are dead from here: scratch may land
+        conv_tail<G, true>(lane, lds_w, c1a, p1w, c2w, fw, 0);
+        lstm_step(win);
+        if (has1) {
+            conv_tail<G, true>(lane, lds_w, c1b, p1w, c2w, fw, 0);
+            lstm_step(win1);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Debug: one 16x16x32 bf16 MFMA tile (fragment-map ground truth for tests)
 // ---------------------------------------------------------------------------
 __global__ void debug_mfma_kernel(const unsigned short* __restrict__ A,
@@ -780,9 +1027,61 @@ int launch_lstm(const float* feat, const float* age, float* out,
     return (int)hipGetLastError();
 }
 
+// Fused serving tail: even-CIN variants whose CIN equals the ring's channel
+// count; anything else is SERVE_TAIL_UNSUPPORTED and launches nothing.
+#define SERVE_TAIL_UNSUPPORTED (-6)
+template <class G>
+int launch_serve_tail(const float* proc, int S, int C, int ring, long end_in,
+                      const long long* dstate, int end_extra,
+                      const float* age, float* out, const float* wpack,
+                      const void* bfrag, float age_eps, int apply_sigmoid,
+                      hipStream_t stream) {
+    if constexpr (G::CIN % 2 != 0) {
+        return SERVE_TAIL_UNSUPPORTED;
+    } else {
+        if (C != G::CIN) return SERVE_TAIL_UNSUPPORTED;
+        // a window must fit the ring; row byte offsets are 32-bit
+        if (ring < G::L || ring > (1 << 29)) return -5;
+        if (!bfrag) return -2;
+        if (S <= 0) return 0;
+        // grid as launch_conv's 1-wave-per-2-windows branch
+        int g1 = (S / 2 + WG_WAVES - 1) / WG_WAVES;
+        if (g1 < 1) g1 = 1;
+        if (g1 > 8192) g1 = 8192;
+        hipLaunchKernelGGL((serve_tail_kernel<G>), dim3(g1),
+                           dim3(WG_THREADS), 0, stream, proc, age, out, wpack,
+                           (const unsigned short*)bfrag, S, ring, end_in,
+                           dstate, end_extra, age_eps, apply_sigmoid);
+        return (int)hipGetLastError();
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+// Window gather + conv + one LSTM step + head from the (S, C, G) fp32 ring;
+// end = dstate ? dstate[1] + end_extra : end_in (as in the window gather).
+int tskd_serve_tail_fwd(const float* proc, int S, int C, int G, long end_in,
+                        const long long* dstate, int end_extra,
+                        const float* age, float* out, const float* wpack,
+                        const void* bfrag, float age_eps, int apply_sigmoid,
+                        int variant, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    switch (variant) {
+        case 0: return launch_serve_tail<GeomCNN5>(
+                    proc, S, C, G, end_in, dstate, end_extra, age, out, wpack,
+                    bfrag, age_eps, apply_sigmoid, s);
+        case 1: return launch_serve_tail<GeomCNN2>(
+                    proc, S, C, G, end_in, dstate, end_extra, age, out, wpack,
+                    bfrag, age_eps, apply_sigmoid, s);
+        case 2: return launch_serve_tail<GeomCNN4>(
+                    proc, S, C, G, end_in, dstate, end_extra, age, out, wpack,
+                    bfrag, age_eps, apply_sigmoid, s);
+    }
+    return -1;
+}
+
 
 // variant: 0 = MyCNN5, 1 = MyCNN2/3, 2 = MyCNN4
 int tskd_conv_fwd(const void* x, int x_is_bf16, int x_timelast, float* feat,
