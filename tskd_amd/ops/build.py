@@ -20,6 +20,7 @@ SOURCES = {
     "_tskd_preprocess": ["preprocess_kernels.hip"],
     "_tskd_train": ["train_kernels.hip"],
 }
+HEADERS = ["tskd_common.h"]  # included by every .hip above
 
 
 def lib_path(name: str) -> str:
@@ -40,8 +41,10 @@ def build(name: str, force: bool = False, verbose: bool = True) -> str:
         raise FileNotFoundError(missing)
     out = lib_path(name)
     os.makedirs(LIB_DIR, exist_ok=True)
+    # the shared header is a dependency of every library
+    deps = srcs + [os.path.join(CSRC, h) for h in HEADERS]
     if not force and os.path.exists(out) and all(
-        os.path.getmtime(out) >= os.path.getmtime(s) for s in srcs
+        os.path.getmtime(out) >= os.path.getmtime(d) for d in deps
     ):
         return out
     cmd = [

@@ -1,22 +1,27 @@
 // MyCNN fused inference kernels — hand-written CDNA4 (gfx950 / MI355X) HIP.
 //
 // Replaces the reference's PyTorch ATen CPU ops (reference bin/models.py:22-36;
-// SURVEY.md §2.6 K1-K9) with two fused kernels:
+// SURVEY.md §2.6 K1-K9). Geometry, pack offsets and the small device helpers
+// shared with the other two libraries are in tskd_common.h.
 //
-//   1. conv_stack_*_kernel: (SN, CIN, 120) windows -> (SN, LIN) features.
-//      Fuses Conv1d(CIN,4,K1) + tanh + MaxPool1d(PK,PS) + Conv1d(4,1,5) +
-//      tanh + pool into ONE kernel: one 64-lane wavefront per window.
-//      Two compute paths:
-//        - bf16 input (the serving path): conv1 as an MFMA im2col-GEMM.
-//          The window is staged TRANSPOSED in LDS as bf16 (xt[t][i]), which
-//          makes the im2col matrix A[s][kk] (kk = k*CIN + i) a simple
-//          shifted view xt_flat[s*CIN + kk] — A fragments are contiguous
-//          LDS reads, no gather. B = conv weights pre-packed host-side in
-//          MFMA fragment order (4 used columns of a 16-col tile); the
-//          v_mfma_f32_16x16x32_bf16 accumulator chains over KK/32 k-steps,
-//          epilogue adds bias + tanh and lands rows in LDS for the pool.
-//        - fp32 input (exact-numerics path): direct VALU cross-correlation.
-//      Dropout sites are identity in eval (K5).
+//   1. Conv stack: (SN, CIN, 120) windows -> (SN, LIN) features. Fuses
+//      Conv1d(CIN,4,K1) + tanh + MaxPool1d(PK,PS) + Conv1d(4,1,5) + tanh +
+//      pool into ONE kernel, one 64-lane wavefront per window; the pooled
+//      tail (conv_tail) is shared. Dropout sites are identity in eval (K5).
+//        1a conv_stack_kernel — fp32 input (exact-numerics path): direct
+//           VALU cross-correlation.
+//        1b conv_stack_mfma_kernel — bf16 (SN, CIN, L) input: conv1 as an
+//           MFMA im2col-GEMM. The window is staged TRANSPOSED in LDS as bf16
+//           (xt[t][i]), which makes the im2col matrix A[s][kk]
+//           (kk = k*CIN + i) a shifted view xt_flat[s*CIN + kk] — A
+//           fragments are contiguous LDS reads, no gather. B = conv weights
+//           pre-packed host-side in MFMA fragment order (4 used columns of a
+//           16-col tile); the v_mfma_f32_16x16x32_bf16 accumulator chains
+//           over KK/32 k-steps; the epilogue folds the bias and lands RAW
+//           rows in LDS for the pool (tanh is applied after each pool).
+//        1c conv_stack_mfma_tlast_kernel — bf16 time-last (SN, L, CIN)
+//           input, even CIN: the same GEMM with A fragments read straight
+//           from global, one wave per TWO windows.
 //
 //   2. lstm_head_kernel: (S, N, LIN) features -> (S, N) logits/probs.
 //      Fuses the 2-layer LSTM(LIN,16) *batch-axis-as-time* scan (the
@@ -28,87 +33,45 @@
 //      are collected into per-lane registers with 16 INDEPENDENT shuffles
 //      per layer (dependency-chain broken: the serial-scan critical path is
 //      ~2 shuffle round-trips per layer, not 32), features prefetched into
-//      LDS in CHUNK-step blocks.
+//      LDS in 32-step chunks.
+//
+//   3. serve_tail_kernel: the serving trigger (one window per stream) as one
+//      kernel — window gather from the fp32 ring + 1b's conv + ONE LSTM step
+//      + head. MyCNN5/MyCNN4 (even CIN).
+//
+//   debug_mfma_kernel: one 16x16x32 bf16 MFMA tile, the fragment-map ground
+//   truth for the tests.
 //
 // Numerics: fp32 accumulation throughout (MFMA accumulator is fp32).
 // Wavefront size is 64 on CDNA4 (not 32) — all lane math assumes it.
 
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
-#define WAVE 64
+#include "tskd_common.h"
+
 #define WG_WAVES 4
 #define WG_THREADS (WAVE * WG_WAVES)
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// ---------------------------------------------------------------------------
-// Geometry per model variant (lengths from SURVEY.md §2.3 forward semantics)
-// ---------------------------------------------------------------------------
-template <int CIN_, int K1_, int PK_, int PS_, int L_ = 120>
-struct Geom {
-    static constexpr int CIN = CIN_;
-    static constexpr int K1  = K1_;
-    static constexpr int PK  = PK_;
-    static constexpr int PS  = PS_;
-    static constexpr int L   = L_;
-    static constexpr int C1  = L - K1 + 1;            // conv1 out len
-    static constexpr int P1  = (C1 - PK) / PS + 1;    // pool1 out len
-    static constexpr int C2  = P1 - 5 + 1;            // conv2 out len (k=5)
-    static constexpr int LIN = (C2 - PK) / PS + 1;    // pool2 out len = LSTM in
-    // MFMA im2col geometry
-    static constexpr int KK     = CIN * K1;           // reduction length
-    static constexpr int KSTEPS = (KK + 31) / 32;     // mfma k-steps (K=32)
-    static constexpr int MTILES = (C1 + 15) / 16;     // 16-row output tiles
-    static constexpr int XTN    = CIN * L;            // transposed window elems
-    static constexpr int XTSZ   = ((MTILES * 16 - 1) * CIN + KSTEPS * 32 + 7)
-                                  / 8 * 8;            // padded LDS extent
-    // fp32 weight-pack offsets (must match tskd_amd/ops/pack.py)
-    static constexpr int OW1   = 0;                   // [4][CIN][K1]
-    static constexpr int OB1   = OW1 + 4 * CIN * K1;  // [4]
-    static constexpr int OW2   = OB1 + 4;             // [4][5]
-    static constexpr int OB2   = OW2 + 20;            // [1]
-    static constexpr int OWIH1 = OB2 + 1;             // [64][LIN]
-    static constexpr int OWHH1 = OWIH1 + 64 * LIN;    // [64][16]
-    static constexpr int OBL1  = OWHH1 + 64 * 16;     // [64] (b_ih + b_hh)
-    static constexpr int OWIH2 = OBL1 + 64;           // [64][16]
-    static constexpr int OWHH2 = OWIH2 + 64 * 16;     // [64][16]
-    static constexpr int OBL2  = OWHH2 + 64 * 16;     // [64]
-    static constexpr int OOUTW = OBL2 + 64;           // [16]
-    static constexpr int OOUTB = OOUTW + 16;          // [1]
-    static constexpr int NPACK = OOUTB + 1;
-};
+// One lane's MFMA operand fragment: 8 bf16 = 4 dwords.
+union BU { unsigned int d[4]; unsigned short u[8]; bf16x8 v; };
 
-using GeomCNN5 = Geom<10, 10, 3, 2>;  // MyCNN5: 111/55/51/25
-using GeomCNN2 = Geom<7, 5, 2, 2>;    // MyCNN2/3: 116/58/54/27
-using GeomCNN4 = Geom<10, 5, 2, 2>;   // MyCNN4: same lens as CNN2, 10 ch
-
-static_assert(GeomCNN5::LIN == 25, "MyCNN5 feature length must be 25");
-static_assert(GeomCNN2::LIN == 27, "MyCNN2 feature length must be 27");
-static_assert(GeomCNN5::KSTEPS == 4 && GeomCNN2::KSTEPS == 2, "");
-
-// Same-wave LDS read-after-write fence: LDS ops of one wave complete in
-// order once lgkmcnt drains; the asm "memory" clobber stops compiler
-// reordering, wave_barrier stops scheduler migration across it.
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short u) {
-    union { unsigned int i; float f; } v;
-    v.i = ((unsigned int)u) << 16;
-    return v.f;
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) {
-    return 1.0f / (1.0f + __expf(-x));
-}
-
-__device__ __forceinline__ float tanhf_(float x) {
-    // tanh(x) = 2*sigmoid(2x) - 1; fast-exp based, fp32-accurate to ~1e-7 rel.
-    return 2.0f / (1.0f + __expf(-2.0f * x)) - 1.0f;
+// Preload this lane's B fragments for all k-steps: one dwordx4 per step
+// from the host-packed [KSTEPS][64][8] bf16 array.
+template <class G>
+__device__ __forceinline__ void load_bfrags(
+    const unsigned short* bfrag, int lane, bf16x8 (&bfr)[G::KSTEPS])
+{
+    #pragma unroll
+    for (int st = 0; st < G::KSTEPS; ++st) {
+        BU bu;
+        #pragma unroll
+        for (int q = 0; q < 4; ++q)
+            bu.d[q] = ((const unsigned int*)bfrag)[(st * WAVE + lane) * 4 + q];
+        bfr[st] = bu.v;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -172,14 +135,13 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_kernel(
     const float* __restrict__ wpack,
     int SN)
 {
-    constexpr int NW = 4 * G::CIN * G::K1 + 4 + 20 + 1;
-    __shared__ float lds_w[NW];
+    __shared__ float lds_w[G::NW];
     __shared__ float lds_x[WG_WAVES][G::CIN * G::L];
     __shared__ float lds_c1[WG_WAVES][4 * G::C1];
     __shared__ float lds_p1[WG_WAVES][4 * G::P1];
     __shared__ float lds_c2[WG_WAVES][G::C2];
 
-    for (int i = threadIdx.x; i < NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    for (int i = threadIdx.x; i < G::NW; i += WG_THREADS) lds_w[i] = wpack[i];
     __syncthreads();
 
     const float* w1 = lds_w + G::OW1;
@@ -235,14 +197,13 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_kernel(
     const unsigned short* __restrict__ bfrag,  // [KSTEPS][64][8] bf16 bits
     int SN)
 {
-    constexpr int NW = 4 * G::CIN * G::K1 + 4 + 20 + 1;
-    __shared__ float lds_w[NW];
+    __shared__ float lds_w[G::NW];
     __shared__ unsigned short lds_xt[WG_WAVES][G::XTSZ];  // transposed window
     __shared__ float lds_c1[WG_WAVES][4 * G::C1];
     __shared__ float lds_p1[WG_WAVES][4 * G::P1];
     __shared__ float lds_c2[WG_WAVES][G::C2];
 
-    for (int i = threadIdx.x; i < NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    for (int i = threadIdx.x; i < G::NW; i += WG_THREADS) lds_w[i] = wpack[i];
     __syncthreads();
 
     const int wave = threadIdx.x / WAVE;
@@ -250,9 +211,10 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_kernel(
     const float* b1 = lds_w + G::OB1;
     unsigned short* xt = lds_xt[wave];
 
-    // Preload B fragments (per-lane, all k-steps): one dwordx4 per step.
     bf16x8 bfr[G::KSTEPS];
-    union BU { unsigned int d[4]; unsigned short u[8]; bf16x8 v; };
+    // Preload B fragments (per-lane, all k-steps): one dwordx4 per step.
+    // Written out rather than load_bfrags(): the helper's loop form changes
+    // this kernel's instruction schedule.
     #pragma unroll
     for (int st = 0; st < G::KSTEPS; ++st) {
         BU bu;
@@ -306,8 +268,6 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_kernel(
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(au.v, bfr[st],
                                                               acc, 0, 0, 0);
             }
-            // epilogue: bias-folded RAW pre-activations; tanh is applied
-            // after pool1 (monotonicity) in conv_tail<., true>
             const int c = lane & 15;
             if (c < 4) {
                 #pragma unroll
@@ -349,13 +309,12 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_tlast_kernel(
     const unsigned short* __restrict__ bfrag,  // [KSTEPS][64][8] bf16 bits
     int SN)
 {
-    constexpr int NW = 4 * G::CIN * G::K1 + 4 + 20 + 1;
-    __shared__ float lds_w[NW];
+    __shared__ float lds_w[G::NW];
     __shared__ float lds_c1[WG_WAVES][4 * G::C1];
     __shared__ float lds_p1[WG_WAVES][4 * G::P1];
     __shared__ float lds_c2[WG_WAVES][G::C2];
 
-    for (int i = threadIdx.x; i < NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    for (int i = threadIdx.x; i < G::NW; i += WG_THREADS) lds_w[i] = wpack[i];
     __syncthreads();
 
     const int wave = threadIdx.x / WAVE;
@@ -363,15 +322,7 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_tlast_kernel(
     const float* b1 = lds_w + G::OB1;
 
     bf16x8 bfr[G::KSTEPS];
-    union BU { unsigned int d[4]; unsigned short u[8]; bf16x8 v; };
-    #pragma unroll
-    for (int st = 0; st < G::KSTEPS; ++st) {
-        BU bu;
-        #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            bu.d[q] = ((const unsigned int*)bfrag)[(st * WAVE + lane) * 4 + q];
-        bfr[st] = bu.v;
-    }
+    load_bfrags<G>(bfrag, lane, bfr);
     // per-lane fragment base within a window (dwords): rows l&15, k-group l>>4
     const int lane_dw = ((lane & 15) * G::CIN + (lane >> 4) * 8) / 2;
     __shared__ float lds_c1b[WG_WAVES][4 * G::C1];  // 2nd window of the pair
@@ -434,110 +385,6 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_tlast_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Kernel 1d (bf16 TIME-LAST, workgroup-per-window): all 4 waves of a WG
-// cooperate on ONE window — waves split the 7 conv1 M-tiles, the pooled
-// tail runs WG-wide — dividing the per-window serial-latency chain ~4x at
-// the same instruction count. Tiny LDS (one window's intermediates) keeps
-// occupancy at the wave cap.
-// ---------------------------------------------------------------------------
-template <class G>
-__global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_wg_kernel(
-    const unsigned short* __restrict__ x,   // (SN, L, CIN) bf16 bits
-    float* __restrict__ feat,               // (SN, LIN)
-    const float* __restrict__ wpack,
-    const unsigned short* __restrict__ bfrag,
-    int SN)
-{
-    constexpr int NW = 4 * G::CIN * G::K1 + 4 + 20 + 1;
-    __shared__ float lds_w[NW];
-    __shared__ float lds_c1[4 * G::C1];
-    __shared__ float lds_p1[4 * G::P1];
-    __shared__ float lds_c2[G::C2];
-
-    for (int i = threadIdx.x; i < NW; i += WG_THREADS) lds_w[i] = wpack[i];
-    __syncthreads();
-
-    const int wave = threadIdx.x / WAVE;
-    const int lane = threadIdx.x % WAVE;
-    const float* b1 = lds_w + G::OB1;
-    const float* w2 = lds_w + G::OW2;
-    const float b2 = lds_w[G::OB2];
-
-    bf16x8 bfr[G::KSTEPS];
-    union BU { unsigned int d[4]; unsigned short u[8]; bf16x8 v; };
-    #pragma unroll
-    for (int st = 0; st < G::KSTEPS; ++st) {
-        BU bu;
-        #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            bu.d[q] = ((const unsigned int*)bfrag)[(st * WAVE + lane) * 4 + q];
-        bfr[st] = bu.v;
-    }
-    const int lane_dw = ((lane & 15) * G::CIN + (lane >> 4) * 8) / 2;
-
-    for (long win = blockIdx.x; win < SN; win += gridDim.x) {
-        const unsigned int* xw =
-            (const unsigned int*)(x + win * (long)(G::L * G::CIN));
-        // waves split the M-tiles
-        for (int mt = wave; mt < G::MTILES; mt += WG_WAVES) {
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            const unsigned int* base = xw + (long)mt * (16 * G::CIN / 2)
-                                       + lane_dw;
-            #pragma unroll
-            for (int st = 0; st < G::KSTEPS; ++st) {
-                BU au;
-                au.d[0] = base[st * 16 + 0];
-                au.d[1] = base[st * 16 + 1];
-                au.d[2] = base[st * 16 + 2];
-                au.d[3] = base[st * 16 + 3];
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(au.v, bfr[st],
-                                                              acc, 0, 0, 0);
-            }
-            const int c = lane & 15;
-            if (c < 4) {
-                #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int row = mt * 16 + (lane >> 4) * 4 + r;
-                    if (row < G::C1)
-                        lds_c1[c * G::C1 + row] = acc[r] + b1[c];
-                }
-            }
-        }
-        __syncthreads();
-        // WG-wide pooled tail (tanh after pool — monotonicity)
-        for (int o = threadIdx.x; o < 4 * G::P1; o += WG_THREADS) {
-            const int c = o / G::P1, q = o % G::P1;
-            const float* src = lds_c1 + c * G::C1 + q * G::PS;
-            float m = src[0];
-            #pragma unroll
-            for (int k = 1; k < G::PK; ++k) m = fmaxf(m, src[k]);
-            lds_p1[o] = tanhf_(m);
-        }
-        __syncthreads();
-        for (int s = threadIdx.x; s < G::C2; s += WG_THREADS) {
-            float acc = b2;
-            #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* pr = lds_p1 + c * G::P1 + s;
-                #pragma unroll
-                for (int k = 0; k < 5; ++k)
-                    acc = fmaf(w2[c * 5 + k], pr[k], acc);
-            }
-            lds_c2[s] = acc;
-        }
-        __syncthreads();
-        for (int q = threadIdx.x; q < G::LIN; q += WG_THREADS) {
-            const float* src = lds_c2 + q * G::PS;
-            float m = src[0];
-            #pragma unroll
-            for (int k = 1; k < G::PK; ++k) m = fmaxf(m, src[k]);
-            feat[win * G::LIN + q] = tanhf_(m);
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------
 // Kernel 2: fused LSTM (batch-as-time) + Linear head + age gate (+sigmoid)
 // (K6+K7+K8+K9 of SURVEY.md §2.6)
 // ---------------------------------------------------------------------------
@@ -546,7 +393,7 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_wg_kernel(
 // (PyTorch gate order) for hidden units u = l & 15.  After each step the
 // full 16-wide h vectors are collected into per-lane register arrays with
 // 16 independent shuffles, so the next step's h-dots are register FMAs.
-template <class G, int CHUNK = 32>
+template <class G>
 __global__ __launch_bounds__(WG_THREADS) void lstm_head_kernel(
     const float* __restrict__ feat,  // (S, N, LIN)
     const float* __restrict__ age,   // (S, N) or nullptr
@@ -555,6 +402,7 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_head_kernel(
     int S, int N, float age_eps, int apply_sigmoid)
 {
     constexpr int LIN = G::LIN;
+    constexpr int CHUNK = 32;  // feature-prefetch steps (64 measured equal)
     constexpr int PRE_R = (CHUNK * LIN + WAVE - 1) / WAVE;  // regs per lane
     __shared__ float lds_feat[WG_WAVES][CHUNK * LIN];
 
@@ -574,7 +422,6 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_head_kernel(
         wih2[i] = wpack[G::OWIH2 + lane * 16 + i];
         whh2[i] = wpack[G::OWHH2 + lane * 16 + i];
     }
-    const float outw = wpack[G::OOUTW + unit];
     const float outb = wpack[G::OOUTB];
     const bool is_cell_gate = (lane >= 32 && lane < 48);
 
@@ -680,7 +527,6 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_head_kernel(
             wave_sync();  // before overwriting the feature chunk
         }
     }
-    (void)outw;
 }
 
 // ---------------------------------------------------------------------------
@@ -708,14 +554,6 @@ __global__ __launch_bounds__(WG_THREADS) void lstm_head_kernel(
 //           zeros there and are omitted (whh1/whh2 are never loaded); every
 //           kept term keeps its order, so results match the unfused chain.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned int f32_to_bf16_rne(float f) {
-    // same rounding as f32_to_bf16_ in preprocess_kernels.hip
-    union { float f; unsigned int i; } u;
-    u.f = f;
-    const unsigned int r = u.i + 0x7fffu + ((u.i >> 16) & 1);
-    return r >> 16;
-}
-
 template <class G>
 __global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_kernel(
     const float* __restrict__ proc,   // (S, CIN, ring) fp32 processed ring
@@ -728,18 +566,17 @@ __global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_kernel(
 {
     static_assert(G::CIN % 2 == 0, "packed staging needs an even CIN");
     static_assert(G::XTSZ % 8 == 0 && G::XTN % 2 == 0, "");
-    constexpr int NW  = 4 * G::CIN * G::K1 + 4 + 20 + 1;
     constexpr int LIN = G::LIN;
     constexpr int CD  = G::CIN / 2;    // dwords per time-major row
     constexpr int XTD = G::XTSZ / 2;   // padded image, dwords
-    __shared__ float lds_w[NW];
+    __shared__ float lds_w[G::NW];
     __shared__ unsigned int lds_xt[WG_WAVES][2][XTD];
     __shared__ float lds_c1[WG_WAVES][2][4 * G::C1];
     // pool/conv2 scratch and the feature row live in window a's image, which
     // is dead once the MFMA loop has read it (and is restaged every pair)
     static_assert(4 * G::P1 + G::C2 + LIN <= G::XTN / 2, "scratch > image");
 
-    for (int i = threadIdx.x; i < NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    for (int i = threadIdx.x; i < G::NW; i += WG_THREADS) lds_w[i] = wpack[i];
     __syncthreads();
 
     // wave index is uniform: say so, so ring rows and LDS bases are scalar
@@ -756,15 +593,7 @@ __global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_kernel(
     float* fw = c2w + G::C2;
 
     bf16x8 bfr[G::KSTEPS];
-    union BU { unsigned int d[4]; unsigned short u[8]; bf16x8 v; };
-    #pragma unroll
-    for (int st = 0; st < G::KSTEPS; ++st) {
-        BU bu;
-        #pragma unroll
-        for (int q = 0; q < 4; ++q)
-            bu.d[q] = ((const unsigned int*)bfrag)[(st * WAVE + lane) * 4 + q];
-        bfr[st] = bu.v;
-    }
+    load_bfrags<G>(bfrag, lane, bfr);
     // LSTM / head rows (lane = gate row), once per wave. No whh blocks.
     float wih1[LIN], wih2[16], outw[16];
     const float bl1 = wpack[G::OBL1 + lane];
@@ -825,8 +654,8 @@ __global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_kernel(
                 #pragma unroll
                 for (int c = 0; c < G::CIN; c += 2)
                     xt[(lane + h * WAVE) * CD + (c >> 1)] =
-                        f32_to_bf16_rne(v[h][c]) |
-                        (f32_to_bf16_rne(v[h][c + 1]) << 16);
+                        (unsigned int)f32_to_bf16(v[h][c]) |
+                        ((unsigned int)f32_to_bf16(v[h][c + 1]) << 16);
             }
         }
     };
@@ -937,7 +766,7 @@ __global__ void debug_mfma_kernel(const unsigned short* __restrict__ A,
                                   const unsigned short* __restrict__ B,
                                   float* __restrict__ C) {
     const int lane = threadIdx.x;
-    union BU { unsigned short u[8]; bf16x8 v; } a, b;
+    BU a, b;
     #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int k = (lane >> 4) * 8 + j;
@@ -967,29 +796,14 @@ int launch_conv(const void* x, int x_is_bf16, int x_timelast, float* feat,
         if (!bfrag) return -2;  // bf16 path requires packed B fragments
         if (x_timelast) {
             if constexpr (G::CIN % 2 == 0) {
-                // DEFAULT: 1-wave-per-2-windows. The 4-wave-WG variant
-                // measured equal at 4096x256 but 17% SLOWER at the bench
-                // shape 8192x1024 (gpurun_out/val_infknobs.log) — always
-                // re-A/B at the production shape.
-                int onewave = 1;
-                if (const char* e = getenv("TSKD_CONV_TLAST_1WAVE"))
-                    onewave = atoi(e);
-                if (onewave) {
-                    int g1 = (SN / 2 + WG_WAVES - 1) / WG_WAVES;
-                    if (g1 < 1) g1 = 1;
-                    if (g1 > 8192) g1 = 8192;
-                    hipLaunchKernelGGL((conv_stack_mfma_tlast_kernel<G>),
-                                       dim3(g1), dim3(WG_THREADS), 0, stream,
-                                       (const unsigned short*)x, feat, wpack,
-                                       (const unsigned short*)bfrag, SN);
-                } else {
-                    // 4-wave workgroup per window (A/B reference)
-                    int g2 = SN > 16384 ? 16384 : SN;
-                    hipLaunchKernelGGL((conv_stack_mfma_wg_kernel<G>),
-                                       dim3(g2), dim3(WG_THREADS), 0, stream,
-                                       (const unsigned short*)x, feat, wpack,
-                                       (const unsigned short*)bfrag, SN);
-                }
+                // one wave per two windows
+                int g1 = (SN / 2 + WG_WAVES - 1) / WG_WAVES;
+                if (g1 < 1) g1 = 1;
+                if (g1 > 8192) g1 = 8192;
+                hipLaunchKernelGGL((conv_stack_mfma_tlast_kernel<G>),
+                                   dim3(g1), dim3(WG_THREADS), 0, stream,
+                                   (const unsigned short*)x, feat, wpack,
+                                   (const unsigned short*)bfrag, SN);
                 return (int)hipGetLastError();
             }
             return -4;  // odd-CIN variants: use the staged layout
@@ -1014,16 +828,9 @@ int launch_lstm(const float* feat, const float* age, float* out,
     if (S <= 0 || N <= 0) return 0;
     int grid = (S + WG_WAVES - 1) / WG_WAVES;
     if (grid > 8192) grid = 8192;
-    int chunk = 32;
-    if (const char* e = getenv("TSKD_LSTM_CHUNK")) chunk = atoi(e);
-    if (chunk >= 64)
-        hipLaunchKernelGGL((lstm_head_kernel<G, 64>), dim3(grid),
-                           dim3(WG_THREADS), 0, stream, feat, age, out,
-                           wpack, S, N, age_eps, apply_sigmoid);
-    else
-        hipLaunchKernelGGL((lstm_head_kernel<G, 32>), dim3(grid),
-                           dim3(WG_THREADS), 0, stream, feat, age, out,
-                           wpack, S, N, age_eps, apply_sigmoid);
+    hipLaunchKernelGGL((lstm_head_kernel<G>), dim3(grid), dim3(WG_THREADS), 0,
+                       stream, feat, age, out, wpack, S, N, age_eps,
+                       apply_sigmoid);
     return (int)hipGetLastError();
 }
 
@@ -1060,6 +867,8 @@ int launch_serve_tail(const float* proc, int S, int C, int ring, long end_in,
 
 extern "C" {
 
+// variant (everywhere below): 0 = MyCNN5, 1 = MyCNN2/3, 2 = MyCNN4
+
 // Window gather + conv + one LSTM step + head from the (S, C, G) fp32 ring;
 // end = dstate ? dstate[1] + end_extra : end_in (as in the window gather).
 int tskd_serve_tail_fwd(const float* proc, int S, int C, int G, long end_in,
@@ -1067,51 +876,31 @@ int tskd_serve_tail_fwd(const float* proc, int S, int C, int G, long end_in,
                         const float* age, float* out, const float* wpack,
                         const void* bfrag, float age_eps, int apply_sigmoid,
                         int variant, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    switch (variant) {
-        case 0: return launch_serve_tail<GeomCNN5>(
-                    proc, S, C, G, end_in, dstate, end_extra, age, out, wpack,
-                    bfrag, age_eps, apply_sigmoid, s);
-        case 1: return launch_serve_tail<GeomCNN2>(
-                    proc, S, C, G, end_in, dstate, end_extra, age, out, wpack,
-                    bfrag, age_eps, apply_sigmoid, s);
-        case 2: return launch_serve_tail<GeomCNN4>(
-                    proc, S, C, G, end_in, dstate, end_extra, age, out, wpack,
-                    bfrag, age_eps, apply_sigmoid, s);
-    }
-    return -1;
+    return dispatch_variant(variant, [&](auto g) {
+        return launch_serve_tail<typename decltype(g)::type>(
+            proc, S, C, G, end_in, dstate, end_extra, age, out, wpack, bfrag,
+            age_eps, apply_sigmoid, (hipStream_t)stream);
+    });
 }
 
-
-// variant: 0 = MyCNN5, 1 = MyCNN2/3, 2 = MyCNN4
 int tskd_conv_fwd(const void* x, int x_is_bf16, int x_timelast, float* feat,
                   const float* wpack, const void* bfrag, int SN, int variant,
                   void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    switch (variant) {
-        case 0: return launch_conv<GeomCNN5>(x, x_is_bf16, x_timelast, feat,
-                                             wpack, bfrag, SN, s);
-        case 1: return launch_conv<GeomCNN2>(x, x_is_bf16, x_timelast, feat,
-                                             wpack, bfrag, SN, s);
-        case 2: return launch_conv<GeomCNN4>(x, x_is_bf16, x_timelast, feat,
-                                             wpack, bfrag, SN, s);
-    }
-    return -1;
+    return dispatch_variant(variant, [&](auto g) {
+        return launch_conv<typename decltype(g)::type>(
+            x, x_is_bf16, x_timelast, feat, wpack, bfrag, SN,
+            (hipStream_t)stream);
+    });
 }
 
 int tskd_lstm_head_fwd(const float* feat, const float* age, float* out,
                        const float* wpack, int S, int N, float age_eps,
                        int apply_sigmoid, int variant, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    switch (variant) {
-        case 0: return launch_lstm<GeomCNN5>(feat, age, out, wpack, S, N,
-                                             age_eps, apply_sigmoid, s);
-        case 1: return launch_lstm<GeomCNN2>(feat, age, out, wpack, S, N,
-                                             age_eps, apply_sigmoid, s);
-        case 2: return launch_lstm<GeomCNN4>(feat, age, out, wpack, S, N,
-                                             age_eps, apply_sigmoid, s);
-    }
-    return -1;
+    return dispatch_variant(variant, [&](auto g) {
+        return launch_lstm<typename decltype(g)::type>(
+            feat, age, out, wpack, S, N, age_eps, apply_sigmoid,
+            (hipStream_t)stream);
+    });
 }
 
 int tskd_debug_mfma16x16x32(const unsigned short* A, const unsigned short* B,
@@ -1122,31 +911,19 @@ int tskd_debug_mfma16x16x32(const unsigned short* A, const unsigned short* B,
 }
 
 int tskd_pack_size(int variant) {
-    switch (variant) {
-        case 0: return GeomCNN5::NPACK;
-        case 1: return GeomCNN2::NPACK;
-        case 2: return GeomCNN4::NPACK;
-    }
-    return -1;
+    return dispatch_variant(
+        variant, [](auto g) { return decltype(g)::type::NPACK; });
 }
 
 int tskd_feat_len(int variant) {
-    switch (variant) {
-        case 0: return GeomCNN5::LIN;
-        case 1: return GeomCNN2::LIN;
-        case 2: return GeomCNN4::LIN;
-    }
-    return -1;
+    return dispatch_variant(
+        variant, [](auto g) { return decltype(g)::type::LIN; });
 }
 
 // MFMA B-fragment pack geometry for python (ksteps per variant).
 int tskd_conv_ksteps(int variant) {
-    switch (variant) {
-        case 0: return GeomCNN5::KSTEPS;
-        case 1: return GeomCNN2::KSTEPS;
-        case 2: return GeomCNN4::KSTEPS;
-    }
-    return -1;
+    return dispatch_variant(
+        variant, [](auto g) { return decltype(g)::type::KSTEPS; });
 }
 
 }  // extern "C"

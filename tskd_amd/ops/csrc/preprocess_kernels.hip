@@ -33,16 +33,10 @@
 #include <cstdlib>
 #include <math.h>
 
-#define WAVE 64
+#include "tskd_common.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_;
 typedef __attribute__((ext_vector_type(4))) float f32x4_;
-
-__device__ __forceinline__ float bf16_to_f32_(unsigned short u) {
-    union { unsigned int i; float f; } v;
-    v.i = ((unsigned int)u) << 16;
-    return v.f;
-}
 
 // Device-resident ring indices (hipGraph mode): dstate[0]=head,
 // dstate[1]=nproc. A null dstate falls back to the host-passed values.
@@ -62,12 +56,6 @@ __global__ void advance_state_kernel(long long* dstate, int nb, int np) {
 
 typedef float f32x2p_ __attribute__((ext_vector_type(2)));
 
-// Same-wave LDS RAW fence (see mycnn_kernels.hip wave_sync).
-__device__ __forceinline__ void wsync_() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // ---------------------------------------------------------------------------
 // 1a. Dense ingest: raw (S, CIN, T) -> NB = T/bucket_len new buckets/channel
 // ---------------------------------------------------------------------------
@@ -77,7 +65,7 @@ __device__ __forceinline__ void wsync_() {
 // busy (78/16 = 4.9 balanced iterations per group).
 #define ING_GRP 4   // buckets per wave
 #define ING_GL 16   // lanes per bucket group
-template <class DT, int IMODE = 5>
+template <class DT>
 __global__ void ingest_dense_kernel(
     const DT* __restrict__ raw,     // (S, CIN, T)
     float* __restrict__ bsum,       // (S, C, G), element stride BST
@@ -110,10 +98,10 @@ __global__ void ingest_dense_kernel(
         const DT* src = raw + ((long)s * CIN + cin) * T +
                         (long)(active ? b : 0) * bucket_len;
         float sum = 0.f, cnt = 0.f;
-        // 16B-aligned vector body with scalar head/tail peel (bucket offsets
-        // like 625 samples are not 16B-aligned).
+        // 16B-aligned vector body (bucket offsets like 625 samples are not
+        // 16B-aligned): bf16 masks the boundary chunks, fp32 peels them.
         if (active) {
-            if constexpr (IMODE == 5 && sizeof(DT) == 2) {
+            if constexpr (sizeof(DT) == 2) {
                 // peel-free: cover the bucket with ALIGNED oct-chunks and
                 // mask the (at most two) boundary chunks in-register —
                 // removes both scalar peel loops per bucket
@@ -147,7 +135,7 @@ __global__ void ingest_dense_kernel(
                         if (idx0 >= 0 && idx0 + 8 <= bucket_len) {
                             #pragma unroll
                             for (int j = 0; j < 8; ++j) {
-                                const float f = bf16_to_f32_(v[u].h[j]);
+                                const float f = bf16_to_f32(v[u].h[j]);
                                 if (!isnan(f)) { sum += f; cnt += 1.f; }
                             }
                         } else {  // boundary chunk: mask by sample index
@@ -155,7 +143,7 @@ __global__ void ingest_dense_kernel(
                             for (int j = 0; j < 8; ++j) {
                                 const unsigned k = (unsigned)(idx0 + j);
                                 if (k < (unsigned)bucket_len) {
-                                    const float f = bf16_to_f32_(v[u].h[j]);
+                                    const float f = bf16_to_f32(v[u].h[j]);
                                     if (!isnan(f)) { sum += f; cnt += 1.f; }
                                 }
                             }
@@ -165,124 +153,9 @@ __global__ void ingest_dense_kernel(
                 if (at_end)
                     for (int i = nch * 8 - mis + lane; i < bucket_len;
                          i += ING_GL) {  // tensor-final bucket only
-                        const float f = bf16_to_f32_(su[i]);
+                        const float f = bf16_to_f32(su[i]);
                         if (!isnan(f)) { sum += f; cnt += 1.f; }
                     }
-            } else if constexpr (sizeof(DT) == 2) {
-                int pre = (int)(((16 - ((size_t)src & 15)) & 15) / 2);
-                if (pre > bucket_len) pre = bucket_len;
-                for (int i = lane; i < pre; i += ING_GL) {
-                    const float f = bf16_to_f32_((unsigned short)src[i]);
-                    if (!isnan(f)) { sum += f; cnt += 1.f; }
-                }
-                const int oct = (bucket_len - pre) / 8;
-                const u32x4_* vp = (const u32x4_*)((const unsigned short*)src + pre);
-                if constexpr (IMODE == 1 || IMODE == 4) {
-                    // 5-deep load ILP with per-element NaN selects; mode 4
-                    // splits the accumulation across two chains (even/odd
-                    // element) — the single 40-add chain is the lane's
-                    // critical path once loads are in flight
-                    float s1 = 0.f, n1 = 0.f;
-                    for (int base = lane; base < oct; base += 5 * ING_GL) {
-                        union { u32x4_ q; unsigned short h[8]; } v[5];
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            const int pp = base + u * ING_GL;
-                            v[u].q = __builtin_nontemporal_load(
-                                &vp[pp < oct ? pp : 0]);
-                        }
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            if (base + u * ING_GL < oct) {
-                                #pragma unroll
-                                for (int j = 0; j < 8; ++j) {
-                                    const float f = bf16_to_f32_(v[u].h[j]);
-                                    if constexpr (IMODE == 4) {
-                                        if (j & 1) {
-                                            if (!isnan(f)) { s1 += f;
-                                                             n1 += 1.f; }
-                                            continue;
-                                        }
-                                    }
-                                    if (!isnan(f)) { sum += f; cnt += 1.f; }
-                                }
-                            }
-                        }
-                    }
-                    sum += s1;
-                    cnt += n1;
-                } else if constexpr (IMODE == 2) {
-                    // 5 independent nontemporal loads in flight per lane
-                    // (read-ceiling probe: 1-deep streams measure ~5.9 TB/s,
-                    // 4..5-deep ~7.0 TB/s). Out-of-range lanes re-load chunk
-                    // 0 (clamped index) so the loads issue unconditionally,
-                    // and their contribution is masked after.
-                    //
-                    // NaN handling is DEFERRED: the fast path unpacks each
-                    // dword into its two bf16 lanes with 2 bit-ops + 2 adds
-                    // (vs 5 VALU/element for the select chain — at 7 TB/s
-                    // the select version is VALU-issue-bound). A NaN input
-                    // poisons the group sum; the group then redoes its
-                    // bucket with the exact per-element masked loop (rare:
-                    // NaN means a dropped sample).
-                    float bA = 0.f, bB = 0.f;
-                    for (int base = lane; base < oct; base += 5 * ING_GL) {
-                        union { u32x4_ q; unsigned int d[4]; } v[5];
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            const int pp = base + u * ING_GL;
-                            v[u].q = __builtin_nontemporal_load(
-                                &vp[pp < oct ? pp : 0]);
-                        }
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            if (base + u * ING_GL < oct) {
-                                #pragma unroll
-                                for (int j = 0; j < 4; ++j) {
-                                    const unsigned int d = v[u].d[j];
-                                    bA += __uint_as_float(d << 16);
-                                    bB += __uint_as_float(d & 0xffff0000u);
-                                }
-                            }
-                        }
-                    }
-                    float body = bA + bB;
-                    float chk = body;
-                    #pragma unroll
-                    for (int off = 8; off > 0; off >>= 1)
-                        chk += __shfl_xor(chk, off);
-                    if (!isnan(chk)) {
-                        sum += body;
-                        cnt += 8.f * (float)(oct > lane
-                                             ? (oct - 1 - lane) / ING_GL + 1
-                                             : 0);
-                    } else {  // rare: masked redo of this bucket's body
-                        for (int p = lane; p < oct; p += ING_GL) {
-                            union { u32x4_ q; unsigned short h[8]; } v;
-                            v.q = __builtin_nontemporal_load(&vp[p]);
-                            #pragma unroll
-                            for (int j = 0; j < 8; ++j) {
-                                const float f = bf16_to_f32_(v.h[j]);
-                                if (!isnan(f)) { sum += f; cnt += 1.f; }
-                            }
-                        }
-                    }
-                } else {
-                    for (int p = lane; p < oct; p += ING_GL) {
-                        union { u32x4_ q; unsigned short h[8]; } v;
-                        // raw samples are consumed once: stream past L2
-                        v.q = __builtin_nontemporal_load(&vp[p]);
-                        #pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float f = bf16_to_f32_(v.h[j]);
-                            if (!isnan(f)) { sum += f; cnt += 1.f; }
-                        }
-                    }
-                }
-                for (int i = pre + oct * 8 + lane; i < bucket_len; i += ING_GL) {
-                    const float f = bf16_to_f32_((unsigned short)src[i]);
-                    if (!isnan(f)) { sum += f; cnt += 1.f; }
-                }
             } else {
                 int pre = (int)(((16 - ((size_t)src & 15)) & 15) / 4);
                 if (pre > bucket_len) pre = bucket_len;
@@ -292,70 +165,22 @@ __global__ void ingest_dense_kernel(
                 }
                 const int quad = (bucket_len - pre) / 4;
                 const f32x4_* vp = (const f32x4_*)((const float*)src + pre);
-                if constexpr (IMODE == 1) {
-                    for (int base = lane; base < quad; base += 5 * ING_GL) {
-                        f32x4_ v[5];
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            const int pp = base + u * ING_GL;
-                            v[u] = __builtin_nontemporal_load(
-                                &vp[pp < quad ? pp : 0]);
-                        }
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            if (base + u * ING_GL < quad) {
-                                if (!isnan(v[u].x)) { sum += v[u].x; cnt += 1.f; }
-                                if (!isnan(v[u].y)) { sum += v[u].y; cnt += 1.f; }
-                                if (!isnan(v[u].z)) { sum += v[u].z; cnt += 1.f; }
-                                if (!isnan(v[u].w)) { sum += v[u].w; cnt += 1.f; }
-                            }
-                        }
-                    }
-                } else if constexpr (IMODE == 2) {
-                    // same deferred-NaN fast path as the bf16 body
-                    float bA = 0.f, bB = 0.f;
-                    for (int base = lane; base < quad; base += 5 * ING_GL) {
-                        f32x4_ v[5];
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            const int pp = base + u * ING_GL;
-                            v[u] = __builtin_nontemporal_load(
-                                &vp[pp < quad ? pp : 0]);
-                        }
-                        #pragma unroll
-                        for (int u = 0; u < 5; ++u) {
-                            if (base + u * ING_GL < quad) {
-                                bA += v[u].x + v[u].z;
-                                bB += v[u].y + v[u].w;
-                            }
-                        }
-                    }
-                    float body = bA + bB;
-                    float chk = body;
+                for (int base = lane; base < quad; base += 5 * ING_GL) {
+                    f32x4_ v[5];
                     #pragma unroll
-                    for (int off = 8; off > 0; off >>= 1)
-                        chk += __shfl_xor(chk, off);
-                    if (!isnan(chk)) {
-                        sum += body;
-                        cnt += 4.f * (float)(quad > lane
-                                             ? (quad - 1 - lane) / ING_GL + 1
-                                             : 0);
-                    } else {
-                        for (int p = lane; p < quad; p += ING_GL) {
-                            const f32x4_ v = __builtin_nontemporal_load(&vp[p]);
-                            if (!isnan(v.x)) { sum += v.x; cnt += 1.f; }
-                            if (!isnan(v.y)) { sum += v.y; cnt += 1.f; }
-                            if (!isnan(v.z)) { sum += v.z; cnt += 1.f; }
-                            if (!isnan(v.w)) { sum += v.w; cnt += 1.f; }
-                        }
+                    for (int u = 0; u < 5; ++u) {
+                        const int pp = base + u * ING_GL;
+                        v[u] = __builtin_nontemporal_load(
+                            &vp[pp < quad ? pp : 0]);
                     }
-                } else {
-                    for (int p = lane; p < quad; p += ING_GL) {
-                        const f32x4_ v = __builtin_nontemporal_load(&vp[p]);
-                        if (!isnan(v.x)) { sum += v.x; cnt += 1.f; }
-                        if (!isnan(v.y)) { sum += v.y; cnt += 1.f; }
-                        if (!isnan(v.z)) { sum += v.z; cnt += 1.f; }
-                        if (!isnan(v.w)) { sum += v.w; cnt += 1.f; }
+                    #pragma unroll
+                    for (int u = 0; u < 5; ++u) {
+                        if (base + u * ING_GL < quad) {
+                            if (!isnan(v[u].x)) { sum += v[u].x; cnt += 1.f; }
+                            if (!isnan(v[u].y)) { sum += v[u].y; cnt += 1.f; }
+                            if (!isnan(v[u].z)) { sum += v[u].z; cnt += 1.f; }
+                            if (!isnan(v[u].w)) { sum += v[u].w; cnt += 1.f; }
+                        }
                     }
                 }
                 for (int i = pre + quad * 4 + lane; i < bucket_len; i += ING_GL) {
@@ -377,121 +202,6 @@ __global__ void ingest_dense_kernel(
             const long idx = (((long)s * C + c) * G + bi) * BST;
             bsum[idx] = sum;
             bcnt[idx] = cnt;
-        }
-    }
-}
-
-
-// IMODE=3 experiment: each 16-lane group owns TWO buckets (b and b+4) so a
-// wave keeps 10 independent oct-loads in flight and amortizes the per-task
-// index math / reduce / store bubble over twice the bytes. bf16 only (the
-// serving path); fp32 falls back to the 5-deep kernel in the launcher.
-__global__ void ingest_dense_pair_kernel(
-    const unsigned short* __restrict__ raw, float* __restrict__ bsum,
-    float* __restrict__ bcnt, const int* __restrict__ chan_map,
-    int S, int CIN, int C, int T, int G, int bucket_len, long head_in,
-    const long long* __restrict__ dstate, int BST)
-{
-    const long head = ring_head(dstate, head_in);
-    const int head_mod = (int)(head % G);
-    const int NB = T / bucket_len;
-    const int SPAN = 2 * ING_GRP;                 // 8 buckets per wave
-    const int NBG = (NB + SPAN - 1) / SPAN;
-    const long nwaves = (long)S * CIN * NBG;
-    const int wlane = threadIdx.x % WAVE;
-    const int grp = wlane / ING_GL;
-    const int lane = wlane % ING_GL;
-    for (long w = (long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
-         w < nwaves; w += (long)gridDim.x * (blockDim.x / WAVE)) {
-        const int wi = (int)w;
-        const int bg = wi % NBG;
-        const int wrem = wi / NBG;
-        const int cin = wrem % CIN;
-        const int s = wrem / CIN;
-        const int b0 = bg * SPAN + grp, b1 = b0 + ING_GRP;
-        const bool a0 = b0 < NB, a1 = b1 < NB;
-        const unsigned short* row = raw + ((long)s * CIN + cin) * T;
-        const unsigned short* src0 = row + (long)(a0 ? b0 : 0) * bucket_len;
-        const unsigned short* src1 = row + (long)(a1 ? b1 : 0) * bucket_len;
-        float sum0 = 0.f, cnt0 = 0.f, sum1 = 0.f, cnt1 = 0.f;
-        int pre0 = (int)(((16 - ((size_t)src0 & 15)) & 15) / 2);
-        int pre1 = (int)(((16 - ((size_t)src1 & 15)) & 15) / 2);
-        if (pre0 > bucket_len) pre0 = bucket_len;
-        if (pre1 > bucket_len) pre1 = bucket_len;
-        if (a0)
-            for (int i = lane; i < pre0; i += ING_GL) {
-                const float f = bf16_to_f32_(src0[i]);
-                if (!isnan(f)) { sum0 += f; cnt0 += 1.f; }
-            }
-        if (a1)
-            for (int i = lane; i < pre1; i += ING_GL) {
-                const float f = bf16_to_f32_(src1[i]);
-                if (!isnan(f)) { sum1 += f; cnt1 += 1.f; }
-            }
-        const int oct0 = a0 ? (bucket_len - pre0) / 8 : 0;
-        const int oct1 = a1 ? (bucket_len - pre1) / 8 : 0;
-        const u32x4_* vp0 = (const u32x4_*)(src0 + pre0);
-        const u32x4_* vp1 = (const u32x4_*)(src1 + pre1);
-        const int octm = oct0 > oct1 ? oct0 : oct1;
-        for (int base = lane; base < octm; base += 5 * ING_GL) {
-            union U { u32x4_ q; unsigned short h[8]; } v0[5], v1[5];
-            #pragma unroll
-            for (int u = 0; u < 5; ++u) {
-                const int pp = base + u * ING_GL;
-                v0[u].q = __builtin_nontemporal_load(&vp0[pp < oct0 ? pp : 0]);
-                v1[u].q = __builtin_nontemporal_load(&vp1[pp < oct1 ? pp : 0]);
-            }
-            #pragma unroll
-            for (int u = 0; u < 5; ++u) {
-                const int pp = base + u * ING_GL;
-                if (pp < oct0) {
-                    #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float f = bf16_to_f32_(v0[u].h[j]);
-                        if (!isnan(f)) { sum0 += f; cnt0 += 1.f; }
-                    }
-                }
-                if (pp < oct1) {
-                    #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float f = bf16_to_f32_(v1[u].h[j]);
-                        if (!isnan(f)) { sum1 += f; cnt1 += 1.f; }
-                    }
-                }
-            }
-        }
-        if (a0)
-            for (int i = pre0 + oct0 * 8 + lane; i < bucket_len; i += ING_GL) {
-                const float f = bf16_to_f32_(src0[i]);
-                if (!isnan(f)) { sum0 += f; cnt0 += 1.f; }
-            }
-        if (a1)
-            for (int i = pre1 + oct1 * 8 + lane; i < bucket_len; i += ING_GL) {
-                const float f = bf16_to_f32_(src1[i]);
-                if (!isnan(f)) { sum1 += f; cnt1 += 1.f; }
-            }
-        #pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-            sum0 += __shfl_xor(sum0, off);
-            cnt0 += __shfl_xor(cnt0, off);
-            sum1 += __shfl_xor(sum1, off);
-            cnt1 += __shfl_xor(cnt1, off);
-        }
-        if (lane == 0) {
-            const int c = chan_map[cin];
-            const long rowo = ((long)s * C + c) * G;
-            if (a0) {
-                int bi = head_mod + b0;
-                if (bi >= G) bi -= G;
-                bsum[(rowo + bi) * BST] = sum0;
-                bcnt[(rowo + bi) * BST] = cnt0;
-            }
-            if (a1) {
-                int bi = head_mod + b1;
-                if (bi >= G) bi -= G;
-                bsum[(rowo + bi) * BST] = sum1;
-                bcnt[(rowo + bi) * BST] = cnt1;
-            }
         }
     }
 }
@@ -592,7 +302,7 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
                     lc[i] = bc[idx];
                 }
             }
-            wsync_();
+            wave_sync();
             // lane j: sliding raw-sample mean of window starting at j0+j
             if (lane < jn) {
                 float sum = 0.f, cnt = 0.f;
@@ -602,7 +312,7 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
                 }
                 lv[lane] = (cnt > 0.f) ? sum / cnt : NAN;
             }
-            wsync_();
+            wave_sync();
             // lane 0: ffill scan (order-dependent; jn <= 64 steps)
             if (lane == 0) {
                 for (int j = 0; j < jn; ++j) {
@@ -616,9 +326,9 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
                     }
                 }
             }
-            wsync_();
+            wave_sync();
             if (lane < jn) pr[(phead + j0 + lane) % G] = lv[lane];
-            wsync_();
+            wave_sync();
             carry = __shfl(carry, 0);
         }
         nan_prefix = __shfl(nan_prefix, 0);
@@ -630,15 +340,6 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
         }
         if (lane == 0) last_val[sc] = carry;
     }
-}
-
-
-
-__device__ __forceinline__ unsigned short f32_to_bf16_(float f) {
-    union { float f; unsigned int i; } u;
-    u.f = f;
-    const unsigned int r = u.i + 0x7fffu + ((u.i >> 16) & 1);  // RNE
-    return (unsigned short)(r >> 16);
 }
 
 // Timelast gather v2: one thread per (s, b, t) writes ALL C channels of
@@ -669,9 +370,9 @@ __global__ void window_gather_tlast2_kernel(
             unsigned int* od = (unsigned int*)(out + i * C);
             for (int c = 0; c < C; c += 2) {
                 const unsigned int lo =
-                    ok ? f32_to_bf16_(pr[(long)c * G]) : 0u;
+                    ok ? f32_to_bf16(pr[(long)c * G]) : 0u;
                 const unsigned int hi =
-                    ok ? f32_to_bf16_(pr[(long)(c + 1) * G]) : 0u;
+                    ok ? f32_to_bf16(pr[(long)(c + 1) * G]) : 0u;
                 od[c >> 1] = lo | (hi << 16);
             }
         } else {
@@ -687,7 +388,7 @@ __global__ void window_gather_tlast2_kernel(
 // (stream, channel) rows per wave in 16-lane groups; the <= 51 bucket
 // reads per row are consecutive-address (coalesced within the group) and
 // L1-resident, so no LDS staging — only the 16-value ffill scan goes
-// through LDS. Dispatch in tskd_preproc_window_fill (knob TSKD_FILL16).
+// through LDS. Dispatch in tskd_preproc_window_fill.
 __global__ __launch_bounds__(256) void window_fill16_kernel(
     const float* __restrict__ bsum, const float* __restrict__ bcnt,
     float* __restrict__ proc, float* __restrict__ last_val,
@@ -771,7 +472,7 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
             }
         }
         lv[gl] = val;
-        wsync_();
+        wave_sync();
         if (live && gl == 0) {            // serial ffill scan per group
             for (int j = 0; j < np; ++j) {
                 const float v = lv[j];
@@ -785,7 +486,7 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
             }
             last_val[sc] = carry;
         }
-        wsync_();
+        wave_sync();
         if (live && gl < np) {
             nan_prefix = __shfl(nan_prefix, grp * 16);
             first_val = __shfl(first_val, grp * 16);
@@ -794,7 +495,7 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
                 outv = isnan(first_val) ? 0.f : first_val;
             proc[sc * G + (phead + gl) % G] = outv;
         }
-        wsync_();
+        wave_sync();
     }
 }
 
@@ -839,7 +540,7 @@ __global__ void window_gather_kernel(
             #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long o = ob + (long)(tq * 4 + j) * C + c;
-                if constexpr (sizeof(OT) == 2) out[o] = f32_to_bf16_(v[j]);
+                if constexpr (sizeof(OT) == 2) out[o] = f32_to_bf16(v[j]);
                 else out[o] = (OT)v[j];
             }
         } else {
@@ -847,7 +548,7 @@ __global__ void window_gather_kernel(
             if constexpr (sizeof(OT) == 2) {
                 union { unsigned short h[4]; unsigned long long u; } pk;
                 #pragma unroll
-                for (int j = 0; j < 4; ++j) pk.h[j] = f32_to_bf16_(v[j]);
+                for (int j = 0; j < 4; ++j) pk.h[j] = f32_to_bf16(v[j]);
                 *(unsigned long long*)(out + o) = pk.u;
             } else {
                 float4 pk = {v[0], v[1], v[2], v[3]};
@@ -875,7 +576,7 @@ __global__ void window_znorm_kernel(OT* __restrict__ w,  // (rows, WIN)
         float sum = 0.f, sq = 0.f;
         for (int t = lane; t < WIN; t += WAVE) {
             float v;
-            if constexpr (sizeof(OT) == 2) v = bf16_to_f32_((unsigned short)row[t]);
+            if constexpr (sizeof(OT) == 2) v = bf16_to_f32((unsigned short)row[t]);
             else v = (float)row[t];
             sum += v;
             sq = fmaf(v, v, sq);
@@ -890,10 +591,10 @@ __global__ void window_znorm_kernel(OT* __restrict__ w,  // (rows, WIN)
         const float inv = 1.0f / fmaxf(sqrtf(var), eps);
         for (int t = lane; t < WIN; t += WAVE) {
             float v;
-            if constexpr (sizeof(OT) == 2) v = bf16_to_f32_((unsigned short)row[t]);
+            if constexpr (sizeof(OT) == 2) v = bf16_to_f32((unsigned short)row[t]);
             else v = (float)row[t];
             v = (v - mean) * inv;
-            if constexpr (sizeof(OT) == 2) row[t] = (OT)f32_to_bf16_(v);
+            if constexpr (sizeof(OT) == 2) row[t] = (OT)f32_to_bf16(v);
             else row[t] = (OT)v;
         }
     }
@@ -931,61 +632,18 @@ int tskd_preproc_ingest_dense(const void* raw, int raw_is_bf16,
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     const int grid = (int)blocks;
-    // TSKD_INGEST_ILP: 0 = 1-deep select loop, 1 = 5-deep ILP + scalar
-    // peel, 2 = deferred-NaN packed, 3 = paired-bucket, 4 = dual-acc,
-    // 5 (default, bf16) = 5-deep ILP + masked boundary chunks (no scalar
-    // peel; within-run A/B: beats 1 by 6.9%; fp32 falls back to 1).
-    int mode = 5;
-    if (const char* ilp = getenv("TSKD_INGEST_ILP")) mode = atoi(ilp);
-    if (raw_is_bf16) {
-        const unsigned short* rp = (const unsigned short*)raw;
-        if (mode == 3) {
-            hipLaunchKernelGGL(ingest_dense_pair_kernel, dim3(grid), dim3(256),
-                               0, st, rp, bsum, bcnt, chan_map, S, CIN, C, T,
-                               G, bucket_len, head, dstate, bst);
-            return (int)hipGetLastError();
-        }
-        if (mode == 0)
-            hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, 0>),
-                               dim3(grid), dim3(256), 0, st, rp, bsum, bcnt,
-                               chan_map, S, CIN, C, T, G, bucket_len, head,
-                               dstate, bst);
-        else if (mode == 1)
-            hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, 1>),
-                               dim3(grid), dim3(256), 0, st, rp, bsum, bcnt,
-                               chan_map, S, CIN, C, T, G, bucket_len, head,
-                               dstate, bst);
-        else if (mode == 4)
-            hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, 4>),
-                               dim3(grid), dim3(256), 0, st, rp, bsum, bcnt,
-                               chan_map, S, CIN, C, T, G, bucket_len, head,
-                               dstate, bst);
-        else if (mode == 5)
-            hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, 5>),
-                               dim3(grid), dim3(256), 0, st, rp, bsum, bcnt,
-                               chan_map, S, CIN, C, T, G, bucket_len, head,
-                               dstate, bst);
-        else
-            hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, 2>),
-                               dim3(grid), dim3(256), 0, st, rp, bsum, bcnt,
-                               chan_map, S, CIN, C, T, G, bucket_len, head,
-                               dstate, bst);
-    } else {
-        const float* rp = (const float*)raw;
-        if (mode >= 3) mode = 1;  // fp32: modes 3-5 are bf16-only
-        if (mode == 0)
-            hipLaunchKernelGGL((ingest_dense_kernel<float, 0>), dim3(grid),
-                               dim3(256), 0, st, rp, bsum, bcnt, chan_map, S,
-                               CIN, C, T, G, bucket_len, head, dstate, bst);
-        else if (mode == 1)
-            hipLaunchKernelGGL((ingest_dense_kernel<float, 1>), dim3(grid),
-                               dim3(256), 0, st, rp, bsum, bcnt, chan_map, S,
-                               CIN, C, T, G, bucket_len, head, dstate, bst);
-        else
-            hipLaunchKernelGGL((ingest_dense_kernel<float, 2>), dim3(grid),
-                               dim3(256), 0, st, rp, bsum, bcnt, chan_map, S,
-                               CIN, C, T, G, bucket_len, head, dstate, bst);
-    }
+    // bf16: 5-deep load ILP with masked boundary chunks (no scalar peel);
+    // fp32: 5-deep load ILP with a scalar head/tail peel.
+    if (raw_is_bf16)
+        hipLaunchKernelGGL((ingest_dense_kernel<unsigned short>), dim3(grid),
+                           dim3(256), 0, st, (const unsigned short*)raw, bsum,
+                           bcnt, chan_map, S, CIN, C, T, G, bucket_len, head,
+                           dstate, bst);
+    else
+        hipLaunchKernelGGL((ingest_dense_kernel<float>), dim3(grid),
+                           dim3(256), 0, st, (const float*)raw, bsum, bcnt,
+                           chan_map, S, CIN, C, T, G, bucket_len, head, dstate,
+                           bst);
     return (int)hipGetLastError();
 }
 
@@ -1017,8 +675,7 @@ int tskd_preproc_window_fill(const float* bsum, const float* bcnt, float* proc,
                              int np, int win_buckets,
                              const long long* dstate, int bst, void* stream) {
     if (np <= 0) return 0;
-    const char* f16 = getenv("TSKD_FILL16");
-    if (np <= 16 && !(f16 && f16[0] == '0')) {
+    if (np <= 16) {
         // steady-state: 4 (stream, channel) rows per wave, 16-lane groups
         const long nsc4 = ((long)S * C + 15) / 16;
         hipLaunchKernelGGL(window_fill16_kernel, dim3(grid_for(nsc4, 1)),
@@ -1050,8 +707,7 @@ int tskd_preproc_window_gather(const float* proc, void* out, int out_is_bf16,
     const long n = (long)S * B * C * (WIN / 4);
     if (n <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    const char* g2 = getenv("TSKD_GATHER_TLAST_V2");
-    const bool tlast2 = C % 2 == 0 && !(g2 && g2[0] == '0');
+    const bool tlast2 = C % 2 == 0;  // v2 packs channel pairs into dwords
     const long n2 = (long)S * B * WIN;  // v2: thread per (s, b, t)
     if (out_is_bf16) {
         if (out_timelast && tlast2)
