@@ -89,15 +89,11 @@ class TestFusedTail:
         se = _ring(3, 10, seed=31)
         se.nproc = 200
         ref = se.score_latest(me, None, apply_sigmoid=True).clone()
-        se._dstate = torch.tensor([0, 188], dtype=torch.int64, device="cuda")
-        se._dstate_gather_extra = 12
+        dstate = torch.tensor([0, 188], dtype=torch.int64, device="cuda")
         se.nproc = 0  # must be ignored when the state block is set
-        try:
+        with se.device_state(dstate, gather_extra=12):
             got = se.score_latest(me, None, apply_sigmoid=True)
             torch.cuda.synchronize()
-        finally:
-            se._dstate = None
-            se._dstate_gather_extra = 0
         assert torch.equal(got, ref)
 
     def test_unsupported_variant(self, engines):

@@ -52,8 +52,8 @@ class TestHipForward:
         """Ground-truth check of the v_mfma_f32_16x16x32_bf16 A/B/C lane maps
         (asymmetric operands so a transposed map cannot pass — §5.4 rule 16)."""
         import ctypes
-        from tskd_amd.ops import _load_lib, _stream_ptr
-        lib = _load_lib()
+        from tskd_amd.ops import hip
+        lib = hip.load(hip.MYCNN)
         g = torch.Generator().manual_seed(11)
         A = (torch.randn(16, 32, generator=g) * 0.5).to(torch.bfloat16)
         B = (torch.randn(32, 16, generator=g) * 0.5 +
@@ -62,7 +62,7 @@ class TestHipForward:
         Cd = torch.empty(16, 16, dtype=torch.float32, device="cuda")
         rc = lib.tskd_debug_mfma16x16x32(
             ctypes.c_void_p(Ad.data_ptr()), ctypes.c_void_p(Bd.data_ptr()),
-            ctypes.c_void_p(Cd.data_ptr()), _stream_ptr())
+            ctypes.c_void_p(Cd.data_ptr()), hip.stream_ptr())
         assert rc == 0
         torch.cuda.synchronize()
         ref = A.float() @ B.float()

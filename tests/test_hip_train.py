@@ -91,9 +91,10 @@ class TestHipTraining:
         torch.testing.assert_close(tr.grads, 2 * g1, rtol=1e-4, atol=1e-6)
 
     def test_adam_matches_torch(self):
-        from tskd_amd.train.hip_trainer import _load_train_lib, _p, _sp
+        from tskd_amd.ops import hip
+        from tskd_amd.ops.hip import ptr
         import ctypes
-        lib = _load_train_lib()
+        lib = hip.load(hip.TRAIN)
         torch.manual_seed(9)
         n = 5242
         p0 = torch.randn(n)
@@ -110,16 +111,29 @@ class TestHipTraining:
         v = torch.zeros(n).cuda()
         for step in range(3):
             g = (g0 * (step + 1)).cuda()
-            rc = lib.tskd_train_adam(_p(p_h), _p(g), _p(m), _p(v), n,
+            rc = lib.tskd_train_adam(ptr(p_h), ptr(g), ptr(m), ptr(v), n,
                                      ctypes.c_float(1e-3),
                                      ctypes.c_float(0.9),
                                      ctypes.c_float(0.999),
-                                     ctypes.c_float(1e-8), step + 1, _sp())
+                                     ctypes.c_float(1e-8), step + 1,
+                                     hip.stream_ptr())
             assert rc == 0
             torch.cuda.synchronize()
             assert (g == 0).all()  # grads zeroed by the fused kernel
         torch.testing.assert_close(p_h.cpu(), p_t.detach(), rtol=1e-5,
                                    atol=1e-6)
+
+    def test_failed_launch_raises(self):
+        """A nonzero return code is a RuntimeError naming the entry point,
+        not an assert. dispatch_variant refuses an unknown variant before
+        any launch, so no kernel runs."""
+        from tskd_amd.train.hip_trainer import MyCNNHipTrainer
+        tr = MyCNNHipTrainer(build_model("MyCNN5").eval(), device="cuda")
+        tr.variant = 99
+        x = torch.zeros(1, 2, 10, 120, device="cuda")
+        y = torch.zeros(1, 2, device="cuda")
+        with pytest.raises(RuntimeError, match="tskd_train_conv_fwd"):
+            tr.forward_backward(x, None, y)
 
     def test_training_reduces_loss(self):
         from tskd_amd.train.data import make_synthetic_labeled_windows

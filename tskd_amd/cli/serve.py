@@ -240,10 +240,8 @@ class FusedServer:
                     torch.from_numpy(ta),
                     torch.from_numpy(va),
                     advance_to=advance)
-            elif advance / self.se.bucket_s > self.se.head:
-                self.se._clear_ahead(int(advance / self.se.bucket_s))
-                self.se.head = int(advance / self.se.bucket_s)
-                self.se._refill()
+            else:
+                self.se.advance_watermark(advance)
             t0 = self._stamp("ingest", t0)
             np_new = self.se.nproc - nproc_before
             if self.emit_processed and np_new > 0 and self.pids:

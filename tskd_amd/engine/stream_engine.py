@@ -18,78 +18,15 @@ pandas-free windowing.py, itself tested against the kernels).
 
 from __future__ import annotations
 
-import ctypes
+import contextlib
+import os
 from typing import Optional, Sequence
 
 import numpy as np
-import os
-
 import torch
 
 from tskd_amd.engine import windowing as W
-
-_plib: Optional[ctypes.CDLL] = None
-
-
-def _load_preproc_lib() -> ctypes.CDLL:
-    global _plib
-    if _plib is not None:
-        return _plib
-    import os
-
-    from tskd_amd.ops import build as _build
-    path = _build.lib_path("_tskd_preprocess")
-    if not os.path.exists(path):
-        _build.build("_tskd_preprocess")
-    lib = ctypes.CDLL(path)
-    lib.tskd_preproc_ingest_dense.restype = ctypes.c_int
-    lib.tskd_preproc_ingest_dense.argtypes = [
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.tskd_preproc_advance_state.restype = ctypes.c_int
-    lib.tskd_preproc_advance_state.argtypes = [
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.tskd_preproc_ingest_events.restype = ctypes.c_int
-    lib.tskd_preproc_ingest_events.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-        ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.tskd_preproc_clear_buckets.restype = ctypes.c_int
-    lib.tskd_preproc_clear_buckets.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int, ctypes.c_long, ctypes.c_int, ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.tskd_preproc_window_fill.restype = ctypes.c_int
-    lib.tskd_preproc_window_fill.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
-        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.tskd_preproc_window_znorm.restype = ctypes.c_int
-    lib.tskd_preproc_window_znorm.argtypes = [
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_int,
-        ctypes.c_float, ctypes.c_void_p,
-    ]
-    lib.tskd_preproc_window_gather.restype = ctypes.c_int
-    lib.tskd_preproc_window_gather.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int, ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    _plib = lib
-    return lib
-
-
-def _sptr() -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+from tskd_amd.ops import hip
 
 
 class StreamEngine:
@@ -139,13 +76,54 @@ class StreamEngine:
         self.last_val = torch.full((self.S, self.C), float("nan"), device=dev)
         self._dstate = None  # device [head, nproc] during graph capture/replay
         self._dstate_gather_extra = 0
+        self._cm_cache = {}  # chan_map tuple -> int32 device tensor
+        self._warned_partial = False
+        self._forced_ready = False
         if self._gpu:
-            _load_preproc_lib()
+            hip.load(hip.PREPROC)  # fail here, not at the first launch
 
     def _dstate_ptr(self):
-        if self._dstate is None:
-            return ctypes.c_void_p(0)
-        return ctypes.c_void_p(self._dstate.data_ptr())
+        return hip.ptr(self._dstate)
+
+    @contextlib.contextmanager
+    def device_state(self, dstate: torch.Tensor, gather_extra: int = 0):
+        """Within the block every launch reads the ring position from the
+        device int64[2] ``dstate`` = [head, nproc] block (graph capture and
+        replay) instead of the host indices; the window gather and the
+        fused tail end at ``nproc + gather_extra``."""
+        self._dstate, self._dstate_gather_extra = dstate, gather_extra
+        try:
+            yield
+        finally:
+            self._dstate, self._dstate_gather_extra = None, 0
+
+    def _chan_map_tensor(self, chan_map: Sequence[int]) -> torch.Tensor:
+        key = tuple(chan_map)
+        cm = self._cm_cache.get(key)
+        if cm is None:
+            cm = self._cm_cache[key] = torch.tensor(
+                list(chan_map), dtype=torch.int32, device=self.device)
+        return cm
+
+    def _launch_ingest(self, raw: torch.Tensor, chan_map) -> None:
+        """Dense bucket ingest of contiguous fp32/bf16 ``raw`` at head (the
+        kernel takes the device state block's head when one is set)."""
+        hip.check(hip.load(hip.PREPROC).tskd_preproc_ingest_dense(
+            hip.ptr(raw), int(raw.dtype == torch.bfloat16),
+            hip.ptr(self.bsum), hip.ptr(self.bcnt),
+            hip.ptr(self._chan_map_tensor(chan_map)), self.S, raw.shape[1],
+            self.C, raw.shape[2], self.G, self.bucket_len, self.head,
+            self._dstate_ptr(), self._bst, hip.stream_ptr()),
+            "tskd_preproc_ingest_dense")
+
+    def _launch_fill(self, phead: int, np_new: int) -> None:
+        """Window fill of ``np_new`` grid points from ``phead`` (or from the
+        device state block's nproc when one is set)."""
+        hip.check(hip.load(hip.PREPROC).tskd_preproc_window_fill(
+            hip.ptr(self.bsum), hip.ptr(self.bcnt), hip.ptr(self.proc),
+            hip.ptr(self.last_val), self.S, self.C, self.G, phead, np_new,
+            self.win_buckets, self._dstate_ptr(), self._bst,
+            hip.stream_ptr()), "tskd_preproc_window_fill")
 
     # ------------------------------------------------------------------ ingest
     def ingest_dense(self, raw: torch.Tensor,
@@ -159,7 +137,7 @@ class StreamEngine:
         assert raw.shape[0] == self.S
         cin, t = raw.shape[1], raw.shape[2]
         nb = t // self.bucket_len
-        if t % self.bucket_len and not getattr(self, "_warned_partial", False):
+        if t % self.bucket_len and not self._warned_partial:
             import warnings
             warnings.warn(
                 f"ingest_dense: dropping {t % self.bucket_len} trailing "
@@ -173,28 +151,10 @@ class StreamEngine:
         if chan_map is None:
             chan_map = list(range(cin))
         if self._gpu:
-            lib = _load_preproc_lib()
             raw = raw.contiguous()
-            is_bf16 = 1 if raw.dtype == torch.bfloat16 else 0
-            if not is_bf16 and raw.dtype != torch.float32:
+            if raw.dtype not in (torch.bfloat16, torch.float32):
                 raw = raw.float()
-            key = tuple(chan_map)
-            cm = getattr(self, "_cm_cache", {}).get(key)
-            if cm is None:
-                cm = torch.tensor(list(chan_map), dtype=torch.int32,
-                                  device=self.device)
-                self._cm_cache = getattr(self, "_cm_cache", {})
-                self._cm_cache[key] = cm
-            rc = lib.tskd_preproc_ingest_dense(
-                ctypes.c_void_p(raw.data_ptr()), is_bf16,
-                ctypes.c_void_p(self.bsum.data_ptr()),
-                ctypes.c_void_p(self.bcnt.data_ptr()),
-                ctypes.c_void_p(cm.data_ptr()),
-                self.S, cin, self.C, t, self.G, self.bucket_len,
-                ctypes.c_long(self.head), self._dstate_ptr(), self._bst,
-                _sptr())
-            if rc != 0:
-                raise RuntimeError(f"ingest_dense failed: hipError {rc}")
+            self._launch_ingest(raw, chan_map)
             self._clear_stale_channels(chan_map, nb)
         else:
             rawf = raw.float().cpu().numpy()
@@ -267,20 +227,15 @@ class StreamEngine:
                 self._clear_ahead(bmax + 1)
             else:
                 self._clear_ahead(0)
-            lib = _load_preproc_lib()
             si = stream_idx.to(torch.int32).contiguous().to(self.device)
             ci = chan_idx.to(torch.int32).contiguous().to(self.device)
             bi = bucket_d.contiguous()
             vi = vals.float().contiguous().to(self.device)
-            rc = lib.tskd_preproc_ingest_events(
-                ctypes.c_void_p(si.data_ptr()), ctypes.c_void_p(ci.data_ptr()),
-                ctypes.c_void_p(bi.data_ptr()), ctypes.c_void_p(vi.data_ptr()),
-                ctypes.c_void_p(self.bsum.data_ptr()),
-                ctypes.c_void_p(self.bcnt.data_ptr()),
-                self.C, self.G, ctypes.c_long(len(vi)),
-                ctypes.c_long(min_bucket), self._bst, _sptr())
-            if rc != 0:
-                raise RuntimeError(f"ingest_events failed: hipError {rc}")
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_ingest_events(
+                hip.ptr(si), hip.ptr(ci), hip.ptr(bi), hip.ptr(vi),
+                hip.ptr(self.bsum), hip.ptr(self.bcnt), self.C, self.G,
+                len(vi), min_bucket, self._bst, hip.stream_ptr()),
+                "tskd_preproc_ingest_events")
             if advance_to is None and len(tsd):
                 advance_to = float(tsd.max().item())
         else:
@@ -340,9 +295,15 @@ class StreamEngine:
             self.ingest_events(stream_idx[idx], chan_idx[idx], ts[idx],
                                vals[idx], advance_to=chunk_adv)
             lo = hi
-        if advance_to is not None and advance_to / self.bucket_s > self.head:
-            self._clear_ahead(int(advance_to / self.bucket_s))
-            self.head = int(advance_to / self.bucket_s)
+        if advance_to is not None:
+            self.advance_watermark(advance_to)
+
+    def advance_watermark(self, seconds: float) -> None:
+        """Advance the event-time watermark to ``seconds`` without events:
+        buckets before it become eligible and are processed."""
+        if seconds / self.bucket_s > self.head:
+            self._clear_ahead(int(seconds / self.bucket_s))
+            self.head = int(seconds / self.bucket_s)
             self._refill()
 
     def _clear_ahead(self, upto_bucket: int) -> None:
@@ -353,14 +314,10 @@ class StreamEngine:
         start = max(self._cleared, upto_bucket - self.G)
         nb = upto_bucket - start
         if self._gpu:
-            lib = _load_preproc_lib()
-            rc = lib.tskd_preproc_clear_buckets(
-                ctypes.c_void_p(self.bsum.data_ptr()),
-                ctypes.c_void_p(self.bcnt.data_ptr()),
-                self.S, self.C, self.G, ctypes.c_long(start), nb,
-                self._bst, _sptr())
-            if rc != 0:
-                raise RuntimeError(f"clear_buckets failed: hipError {rc}")
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_clear_buckets(
+                hip.ptr(self.bsum), hip.ptr(self.bcnt), self.S, self.C,
+                self.G, start, nb, self._bst, hip.stream_ptr()),
+                "tskd_preproc_clear_buckets")
         else:
             idx = np.arange(start, start + nb) % self.G
             self.bsum[:, :, idx] = 0
@@ -372,40 +329,13 @@ class StreamEngine:
         Writes buckets [head, head+NB) — DISJOINT from anything the fill
         stage of the PREVIOUS trigger reads, which is what makes the
         two-stream overlapped TriggerGraph legal."""
-        lib = _load_preproc_lib()
-        cin, t = raw.shape[1], raw.shape[2]
-        key = tuple(chan_map)
-        cm = getattr(self, "_cm_cache", {}).get(key)
-        if cm is None:
-            cm = torch.tensor(list(chan_map), dtype=torch.int32,
-                              device=self.device)
-            self._cm_cache = getattr(self, "_cm_cache", {})
-            self._cm_cache[key] = cm
-        is_bf16 = 1 if raw.dtype == torch.bfloat16 else 0
-        rc = lib.tskd_preproc_ingest_dense(
-            ctypes.c_void_p(raw.data_ptr()), is_bf16,
-            ctypes.c_void_p(self.bsum.data_ptr()),
-            ctypes.c_void_p(self.bcnt.data_ptr()),
-            ctypes.c_void_p(cm.data_ptr()),
-            self.S, cin, self.C, t, self.G, self.bucket_len,
-            ctypes.c_long(0), self._dstate_ptr(), self._bst, _sptr())
-        if rc != 0:
-            raise RuntimeError(f"ingest(graph) failed: {rc}")
+        self._launch_ingest(raw, chan_map)
 
     def fill_graph_kernel(self, nb: int) -> None:
         """Capture-safe window fill of nb new grid points (nproc from
         dstate; reads buckets [nproc, nproc+nb+win-1) = through the buckets
         the SAME trigger's ingest just wrote)."""
-        lib = _load_preproc_lib()
-        rc = lib.tskd_preproc_window_fill(
-            ctypes.c_void_p(self.bsum.data_ptr()),
-            ctypes.c_void_p(self.bcnt.data_ptr()),
-            ctypes.c_void_p(self.proc.data_ptr()),
-            ctypes.c_void_p(self.last_val.data_ptr()),
-            self.S, self.C, self.G, ctypes.c_long(0), nb,
-            self.win_buckets, self._dstate_ptr(), self._bst, _sptr())
-        if rc != 0:
-            raise RuntimeError(f"fill(graph) failed: {rc}")
+        self._launch_fill(self.nproc, nb)
 
     def ingest_dense_graph_body(self, raw: torch.Tensor, chan_map, nb: int
                                  ) -> None:
@@ -430,16 +360,7 @@ class StreamEngine:
             self.nproc = navail - max_np
             np_new = max_np
         if self._gpu:
-            lib = _load_preproc_lib()
-            rc = lib.tskd_preproc_window_fill(
-                ctypes.c_void_p(self.bsum.data_ptr()),
-                ctypes.c_void_p(self.bcnt.data_ptr()),
-                ctypes.c_void_p(self.proc.data_ptr()),
-                ctypes.c_void_p(self.last_val.data_ptr()),
-                self.S, self.C, self.G, ctypes.c_long(self.nproc), np_new,
-                self.win_buckets, self._dstate_ptr(), self._bst, _sptr())
-            if rc != 0:
-                raise RuntimeError(f"window_fill failed: hipError {rc}")
+            self._launch_fill(self.nproc, np_new)
         else:
             bs = self.bsum.numpy()
             bc = self.bcnt.numpy()
@@ -484,25 +405,21 @@ class StreamEngine:
         out = out if out is not None else torch.zeros(
             shape, dtype=dtype, device=self.device)
         if self._gpu:
-            lib = _load_preproc_lib()
+            lib = hip.load(hip.PREPROC)
             is_bf16 = 1 if dtype == torch.bfloat16 else 0
             assert dtype in (torch.bfloat16, torch.float32)
-            rc = lib.tskd_preproc_window_gather(
-                ctypes.c_void_p(self.proc.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), is_bf16, int(timelast),
-                self.S, self.C, self.G, B, WIN, stride,
-                ctypes.c_long(self.nproc), self._dstate_ptr(),
-                self._dstate_gather_extra, _sptr())
-            if rc == 0 and znormalize:
+            hip.check(lib.tskd_preproc_window_gather(
+                hip.ptr(self.proc), hip.ptr(out), is_bf16, int(timelast),
+                self.S, self.C, self.G, B, WIN, stride, self.nproc,
+                self._dstate_ptr(), self._dstate_gather_extra,
+                hip.stream_ptr()), "tskd_preproc_window_gather")
+            if znormalize:
                 # opt-in z-normalize per (stream, batch, channel) window row
                 # (NOT reference semantics — see SURVEY.md §7 fidelity note).
                 assert not timelast, "znormalize needs channel-major windows"
-                rc = lib.tskd_preproc_window_znorm(
-                    ctypes.c_void_p(out.data_ptr()), is_bf16,
-                    ctypes.c_long(self.S * B * self.C), WIN,
-                    ctypes.c_float(zeps), _sptr())
-            if rc != 0:
-                raise RuntimeError(f"window_gather failed: hipError {rc}")
+                hip.check(lib.tskd_preproc_window_znorm(
+                    hip.ptr(out), is_bf16, self.S * B * self.C, WIN, zeps,
+                    hip.stream_ptr()), "tskd_preproc_window_znorm")
         else:
             pr = self.proc.numpy()
             if provided:
@@ -539,7 +456,7 @@ class StreamEngine:
         STREAM BEGAN, matching the reference's ~10-minutes-to-first-
         prediction behavior — origin-relative so wall-clock event times
         behave the same as zero-based replay times)."""
-        return getattr(self, "_forced_ready", False) or \
+        return self._forced_ready or \
             self.nproc - self._origin_nproc >= self.model_win
 
     def force_ready(self) -> None:
@@ -593,40 +510,38 @@ class TriggerGraph:
         dev = engine.device
         self.dstate = torch.tensor([engine.head, engine.nproc],
                                    dtype=torch.int64, device=dev)
-        lib = _load_preproc_lib()
-        self._lib = lib
         if overlap:
             self._init_overlap()
             return
-
-        def trigger_body():
-            engine._dstate = self.dstate
-            engine._dstate_gather_extra = self.nb  # gather AFTER fill, pre-advance
-            try:
-                engine.ingest_dense_graph_body(self.raw, self.chan_map,
-                                               self.nb)
-                out = self._score()
-                rc = lib.tskd_preproc_advance_state(
-                    ctypes.c_void_p(self.dstate.data_ptr()), self.nb,
-                    self.nb, _sptr())
-                if rc != 0:
-                    raise RuntimeError(f"advance_state: {rc}")
-                return out
-            finally:
-                engine._dstate = None
-                engine._dstate_gather_extra = 0
-
         # warm side-stream run, then capture
         stream = torch.cuda.Stream()
         with torch.cuda.stream(stream):
-            trigger_body()
+            self._body(True, True)
         torch.cuda.current_stream().wait_stream(stream)
         # the warm run advanced device state AND rings once; mirror it
         engine.head += self.nb
         engine.nproc += self.nb
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = trigger_body()
+            self.out = self._body(True, True)
+
+    def _body(self, ingest: bool, model: bool) -> Optional[torch.Tensor]:
+        """The capturable launch sequence: the ingest stage, the model
+        stage (fill + score), or both, then ONE ring-index advance of the
+        stage(s) run. The gather/fused tail runs AFTER the fill and BEFORE
+        the advance, hence window end = nproc + nb."""
+        engine, nb, out = self.engine, self.nb, None
+        with engine.device_state(self.dstate, nb if model else 0):
+            if ingest:
+                engine.ingest_graph_kernel(self.raw, self.chan_map)
+            if model:
+                engine.fill_graph_kernel(nb)
+                out = self._score()
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_advance_state(
+                hip.ptr(self.dstate), nb if ingest else 0,
+                nb if model else 0, hip.stream_ptr()),
+                "tskd_preproc_advance_state")
+        return out
 
     def _score(self) -> torch.Tensor:
         """Latest-window scores inside a trigger body (after the fill):
@@ -656,52 +571,24 @@ class TriggerGraph:
         raises steady-state throughput by overlapping the HBM-bound ingest
         with the compute-bound model chain.
         """
-        engine, lib = self.engine, self._lib
-        nb = self.nb
-
-        def ingest_body():
-            engine._dstate = self.dstate
-            try:
-                engine.ingest_graph_kernel(self.raw, self.chan_map)
-                rc = lib.tskd_preproc_advance_state(
-                    ctypes.c_void_p(self.dstate.data_ptr()), nb, 0, _sptr())
-                if rc != 0:
-                    raise RuntimeError(f"advance_state(head): {rc}")
-            finally:
-                engine._dstate = None
-
-        def model_body():
-            engine._dstate = self.dstate
-            engine._dstate_gather_extra = nb
-            try:
-                engine.fill_graph_kernel(nb)
-                out = self._score()
-                rc = lib.tskd_preproc_advance_state(
-                    ctypes.c_void_p(self.dstate.data_ptr()), 0, nb, _sptr())
-                if rc != 0:
-                    raise RuntimeError(f"advance_state(nproc): {rc}")
-                return out
-            finally:
-                engine._dstate = None
-                engine._dstate_gather_extra = 0
-
+        engine, nb = self.engine, self.nb
         self._sA = torch.cuda.Stream()
         self._sB = torch.cuda.Stream()
         # warm one full trigger (ingest then model), mirroring host indices
         with torch.cuda.stream(self._sA):
-            ingest_body()
+            self._body(True, False)
         self._sB.wait_stream(self._sA)
         with torch.cuda.stream(self._sB):
-            model_body()
+            self._body(False, True)
         torch.cuda.current_stream().wait_stream(self._sB)
         engine.head += nb
         engine.nproc += nb
         self.graph_i = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_i, stream=self._sA):
-            ingest_body()
+            self._body(True, False)
         self.graph_m = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_m, stream=self._sB):
-            self.out = model_body()
+            self.out = self._body(False, True)
         self._evA = torch.cuda.Event()
 
     def replay(self, raw_refresh: bool = False) -> torch.Tensor:

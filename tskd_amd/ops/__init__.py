@@ -8,73 +8,31 @@ model itself (the numerics oracle the kernels are tested against).
 
 from __future__ import annotations
 
-import ctypes
-import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
-from tskd_amd.ops import build as _build
+from tskd_amd.ops import hip
 from tskd_amd.ops.pack import (VARIANT_IDS, pack_conv1_mfma_bfrags,  # noqa: F401
                                pack_weights)
-
-_lib: Optional[ctypes.CDLL] = None
-_lib_err: Optional[str] = None
-
-
-def _load_lib() -> ctypes.CDLL:
-    global _lib, _lib_err
-    if _lib is not None:
-        return _lib
-    path = _build.lib_path("_tskd_mycnn")
-    if not os.path.exists(path):
-        try:
-            _build.build("_tskd_mycnn")
-        except Exception as e:  # record, raise at use time
-            _lib_err = f"hipcc build failed: {e}"
-            raise RuntimeError(_lib_err)
-    lib = ctypes.CDLL(path)
-    lib.tskd_conv_fwd.restype = ctypes.c_int
-    lib.tskd_conv_fwd.argtypes = [
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.tskd_debug_mfma16x16x32.restype = ctypes.c_int
-    lib.tskd_debug_mfma16x16x32.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-    ]
-    lib.tskd_lstm_head_fwd.restype = ctypes.c_int
-    lib.tskd_lstm_head_fwd.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
-        ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.tskd_serve_tail_fwd.restype = ctypes.c_int
-    lib.tskd_serve_tail_fwd.argtypes = [
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        ctypes.c_long, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-        ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.tskd_pack_size.restype = ctypes.c_int
-    lib.tskd_pack_size.argtypes = [ctypes.c_int]
-    lib.tskd_feat_len.restype = ctypes.c_int
-    lib.tskd_feat_len.argtypes = [ctypes.c_int]
-    _lib = lib
-    return lib
 
 
 def hip_available() -> bool:
     try:
-        _load_lib()
+        hip.load(hip.MYCNN)
         return True
     except Exception:
         return False
 
 
-def _stream_ptr() -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+def _age_ptr(age: Optional[torch.Tensor], s: int, n: int) -> Tuple:
+    """``age`` as a contiguous fp32 (s, n) tensor and its device pointer
+    (None -> null). Returns (pointer, tensor): hold the tensor until the
+    launch."""
+    if age is not None and (age.dtype != torch.float32 or age.shape != (s, n)
+                            or not age.is_contiguous()):
+        age = age.to(torch.float32).expand(s, n).contiguous()
+    return hip.ptr(age), age
 
 
 TLAST_SLACK = 256  # trailing elements the timelast conv kernel may overread
@@ -115,7 +73,7 @@ class MyCNNEngine:
         self.wpack = pack_weights(model).to(self.device)
         self.bfrag = pack_conv1_mfma_bfrags(model).to(self.device)
         if self.device.type == "cuda":
-            lib = _load_lib()  # raises loudly if the HIP ext is unavailable
+            lib = hip.load(hip.MYCNN)  # raises loudly if unavailable
             expect = lib.tskd_pack_size(self.variant)
             if expect != self.wpack.numel():
                 raise RuntimeError(
@@ -140,7 +98,7 @@ class MyCNNEngine:
         sn = xf.shape[0]
         if xf.device.type != "cuda":
             raise RuntimeError("conv_features is the GPU path; use the model on CPU")
-        lib = _load_lib()
+        lib = hip.load(hip.MYCNN)
         if timelast and (self.cin % 2 != 0 or xf.dtype != torch.bfloat16):
             # odd-CIN / fp32: transpose back to the staged layout
             xf = xf.transpose(-1, -2).contiguous()
@@ -158,14 +116,10 @@ class MyCNNEngine:
             pad.reshape(-1).copy_(xf.reshape(-1))
             xf = pad.reshape(sn, 120, self.cin)
         feat = torch.empty(sn, self.feat_len, dtype=torch.float32, device=xf.device)
-        rc = lib.tskd_conv_fwd(
-            ctypes.c_void_p(xf.data_ptr()), is_bf16, int(timelast),
-            ctypes.c_void_p(feat.data_ptr()),
-            ctypes.c_void_p(self.wpack.data_ptr()),
-            ctypes.c_void_p(self.bfrag.data_ptr()), sn, self.variant,
-            _stream_ptr())
-        if rc != 0:
-            raise RuntimeError(f"tskd_conv_fwd failed: hipError {rc}")
+        hip.check(lib.tskd_conv_fwd(
+            hip.ptr(xf), is_bf16, int(timelast), hip.ptr(feat),
+            hip.ptr(self.wpack), hip.ptr(self.bfrag), sn, self.variant,
+            hip.stream_ptr()), "tskd_conv_fwd")
         return feat.reshape(*lead, self.feat_len)
 
     def lstm_head(self, feat: torch.Tensor, age: Optional[torch.Tensor],
@@ -174,22 +128,13 @@ class MyCNNEngine:
         assert feat.dim() == 3 and feat.shape[-1] == self.feat_len
         s, n = feat.shape[0], feat.shape[1]
         feat = feat.contiguous()
-        lib = _load_lib()
+        lib = hip.load(hip.MYCNN)
         out = torch.empty(s, n, dtype=torch.float32, device=feat.device)
-        age_ptr = ctypes.c_void_p(0)
-        if age is not None:
-            if age.dtype != torch.float32 or age.shape != (s, n) \
-                    or not age.is_contiguous():
-                age = age.to(torch.float32).expand(s, n).contiguous()
-            age_ptr = ctypes.c_void_p(age.data_ptr())
-        rc = lib.tskd_lstm_head_fwd(
-            ctypes.c_void_p(feat.data_ptr()), age_ptr,
-            ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_void_p(self.wpack.data_ptr()), s, n,
-            ctypes.c_float(self.age_eps), int(apply_sigmoid), self.variant,
-            _stream_ptr())
-        if rc != 0:
-            raise RuntimeError(f"tskd_lstm_head_fwd failed: hipError {rc}")
+        age_ptr, age = _age_ptr(age, s, n)
+        hip.check(lib.tskd_lstm_head_fwd(
+            hip.ptr(feat), age_ptr, hip.ptr(out), hip.ptr(self.wpack), s, n,
+            self.age_eps, int(apply_sigmoid), self.variant,
+            hip.stream_ptr()), "tskd_lstm_head_fwd")
         return out
 
     def supports_fused_tail(self, n_channels: int) -> bool:
@@ -212,25 +157,15 @@ class MyCNNEngine:
         assert proc.dim() == 3 and proc.dtype == torch.float32 \
             and proc.is_contiguous() and proc.shape[2] == G
         s, c = proc.shape[0], proc.shape[1]
-        lib = _load_lib()
+        lib = hip.load(hip.MYCNN)
         out = torch.empty(s, 1, dtype=torch.float32, device=proc.device)
-        age_ptr = ctypes.c_void_p(0)
-        if age is not None:
-            if age.dtype != torch.float32 or age.shape != (s, 1) \
-                    or not age.is_contiguous():
-                age = age.to(torch.float32).expand(s, 1).contiguous()
-            age_ptr = ctypes.c_void_p(age.data_ptr())
-        rc = lib.tskd_serve_tail_fwd(
-            ctypes.c_void_p(proc.data_ptr()), s, c, int(G),
-            ctypes.c_long(int(end)),
-            dstate_ptr if dstate_ptr is not None else ctypes.c_void_p(0),
-            int(end_extra), age_ptr, ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_void_p(self.wpack.data_ptr()),
-            ctypes.c_void_p(self.bfrag.data_ptr()),
-            ctypes.c_float(self.age_eps), int(apply_sigmoid), self.variant,
-            _stream_ptr())
-        if rc != 0:
-            raise RuntimeError(f"tskd_serve_tail_fwd failed: code {rc}")
+        age_ptr, age = _age_ptr(age, s, 1)
+        hip.check(lib.tskd_serve_tail_fwd(
+            hip.ptr(proc), s, c, int(G), int(end),
+            dstate_ptr if dstate_ptr is not None else hip.ptr(None),
+            int(end_extra), age_ptr, hip.ptr(out), hip.ptr(self.wpack),
+            hip.ptr(self.bfrag), self.age_eps, int(apply_sigmoid),
+            self.variant, hip.stream_ptr()), "tskd_serve_tail_fwd")
         return out
 
     def forward(self, x: torch.Tensor, age: Optional[torch.Tensor] = None,

@@ -19,50 +19,10 @@ from typing import Optional, Tuple
 
 import torch
 
-from tskd_amd.ops import build as _build
+from tskd_amd.ops import hip
+from tskd_amd.ops.hip import check, ptr
 from tskd_amd.ops.pack import (VARIANT_IDS, pack_offsets, pack_weights,
                                unpack_weights_into)
-
-_tlib: Optional[ctypes.CDLL] = None
-
-
-def _load_train_lib() -> ctypes.CDLL:
-    global _tlib
-    if _tlib is not None:
-        return _tlib
-    import os
-    path = _build.lib_path("_tskd_train")
-    if not os.path.exists(path):
-        _build.build("_tskd_train")
-    lib = ctypes.CDLL(path)
-    P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
-    lib.tskd_train_conv_fwd.restype = I
-    lib.tskd_train_conv_fwd.argtypes = [P, P, P, P, I, F, F,
-                                        ctypes.c_ulonglong, I, P]
-    lib.tskd_train_lstm_fwd.restype = I
-    lib.tskd_train_lstm_fwd.argtypes = [P, P, P, P, P, I, I, F, I, P]
-    lib.tskd_train_loss.restype = I
-    lib.tskd_train_loss.argtypes = [P, P, P, P, P, L, F, F, P]
-    lib.tskd_train_lstm_bwd.restype = I
-    lib.tskd_train_lstm_bwd.argtypes = [P, P, P, P, P, P, I, I, I, P]
-    lib.tskd_train_conv_bwd.restype = I
-    lib.tskd_train_conv_bwd.argtypes = [P, P, P, P, P, I, I, P]
-    lib.tskd_train_adam.restype = I
-    lib.tskd_train_adam.argtypes = [P, P, P, P, L, F, F, F, F, I, P]
-    lib.tskd_train_stash_sizes.restype = I
-    lib.tskd_train_stash_sizes.argtypes = [I, P, P]
-    lib.tskd_train_batch_accuracy.restype = I
-    lib.tskd_train_batch_accuracy.argtypes = [P, P, P, L, P]
-    _tlib = lib
-    return lib
-
-
-def _sp() -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t: torch.Tensor) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class MyCNNHipTrainer:
@@ -94,11 +54,10 @@ class MyCNNHipTrainer:
         self._probe_stash_sizes()
 
     def _probe_stash_sizes(self):
-        lib = _load_train_lib()
         cw, lw = ctypes.c_int(), ctypes.c_int()
-        rc = lib.tskd_train_stash_sizes(self.variant, ctypes.byref(cw),
-                                        ctypes.byref(lw))
-        assert rc == 0
+        check(hip.load(hip.TRAIN).tskd_train_stash_sizes(
+            self.variant, ctypes.byref(cw), ctypes.byref(lw)),
+            "tskd_train_stash_sizes")
         self._stash_conv_words = cw.value
         self._stash_lstm_words = lw.value
 
@@ -106,7 +65,7 @@ class MyCNNHipTrainer:
                          y: torch.Tensor) -> float:
         """x (S, B, C, 120) fp32, y (S, B) in {0,1}. Accumulates into grads;
         returns the scalar loss."""
-        lib = _load_train_lib()
+        lib = hip.load(hip.TRAIN)
         assert x.dim() == 4 and x.shape[2] == self.cin and x.shape[3] == 120
         S, B = x.shape[0], x.shape[1]
         SN = S * B
@@ -123,30 +82,25 @@ class MyCNNHipTrainer:
         dlogit = torch.empty(S, B, device=dev)
         dfeat = torch.empty(S, B, self.lin, device=dev)
         loss = torch.zeros(1, device=dev)
-        st = _sp()
-        age_p = _p(age) if age is not None else ctypes.c_void_p(0)
+        st = hip.stream_ptr()
+        age_p = ptr(age)
+        wpack, grads = ptr(self.wpack), ptr(self.grads)
         self.seed += 1  # fresh dropout masks every call
-        rc = lib.tskd_train_conv_fwd(
-            _p(x), _p(feat), _p(stash_c), _p(self.wpack), SN,
-            ctypes.c_float(self.drop1_p), ctypes.c_float(self.drop2_p),
-            ctypes.c_ulonglong(self.seed), self.variant, st)
-        assert rc == 0, f"conv_fwd {rc}"
-        rc = lib.tskd_train_lstm_fwd(_p(feat), age_p, _p(self.wpack),
-                                     _p(stash_l), _p(logits), S, B,
-                                     self.age_eps, self.variant, st)
-        assert rc == 0, f"lstm_fwd {rc}"
-        rc = lib.tskd_train_loss(_p(logits), _p(y), age_p, _p(dlogit),
-                                 _p(loss), SN, self.pos_weight, self.age_eps,
-                                 st)
-        assert rc == 0, f"loss {rc}"
-        rc = lib.tskd_train_lstm_bwd(_p(feat), _p(dlogit), _p(stash_l),
-                                     _p(self.wpack), _p(self.grads),
-                                     _p(dfeat), S, B, self.variant, st)
-        assert rc == 0, f"lstm_bwd {rc}"
-        rc = lib.tskd_train_conv_bwd(_p(x), _p(stash_c), _p(dfeat),
-                                     _p(self.wpack), _p(self.grads), SN,
-                                     self.variant, st)
-        assert rc == 0, f"conv_bwd {rc}"
+        check(lib.tskd_train_conv_fwd(
+            ptr(x), ptr(feat), ptr(stash_c), wpack, SN, self.drop1_p,
+            self.drop2_p, self.seed, self.variant, st), "tskd_train_conv_fwd")
+        check(lib.tskd_train_lstm_fwd(
+            ptr(feat), age_p, wpack, ptr(stash_l), ptr(logits), S, B,
+            self.age_eps, self.variant, st), "tskd_train_lstm_fwd")
+        check(lib.tskd_train_loss(
+            ptr(logits), ptr(y), age_p, ptr(dlogit), ptr(loss), SN,
+            self.pos_weight, self.age_eps, st), "tskd_train_loss")
+        check(lib.tskd_train_lstm_bwd(
+            ptr(feat), ptr(dlogit), ptr(stash_l), wpack, grads, ptr(dfeat),
+            S, B, self.variant, st), "tskd_train_lstm_bwd")
+        check(lib.tskd_train_conv_bwd(
+            ptr(x), ptr(stash_c), ptr(dfeat), wpack, grads, SN, self.variant,
+            st), "tskd_train_conv_bwd")
         return float(loss.item())
 
     def optimizer_step(self) -> None:
@@ -156,12 +110,10 @@ class MyCNNHipTrainer:
             dist.all_reduce(self.grads)
             self.grads /= dist.get_world_size()
         self.step_count += 1
-        lib = _load_train_lib()
-        rc = lib.tskd_train_adam(_p(self.wpack), _p(self.grads), _p(self.m),
-                                 _p(self.v), self.wpack.numel(), self.lr,
-                                 self.betas[0], self.betas[1], self.eps,
-                                 self.step_count, _sp())
-        assert rc == 0, f"adam {rc}"
+        check(hip.load(hip.TRAIN).tskd_train_adam(
+            ptr(self.wpack), ptr(self.grads), ptr(self.m), ptr(self.v),
+            self.wpack.numel(), self.lr, self.betas[0], self.betas[1],
+            self.eps, self.step_count, hip.stream_ptr()), "tskd_train_adam")
 
     def step(self, x, age, y) -> float:
         loss = self.forward_backward(x, age, y)

@@ -42,16 +42,11 @@ def compute_batch_accuracy(output: torch.Tensor,
 def _batch_accuracy_hip(output: torch.Tensor, target: torch.Tensor,
                         batch_size: int) -> torch.Tensor:
     """K14 fused metric kernel (ops/csrc/train_kernels.hip)."""
-    import ctypes
-
-    from tskd_amd.train.hip_trainer import _load_train_lib, _sp
-    lib = _load_train_lib()
+    from tskd_amd.ops import hip
     lo = output.detach().reshape(-1).float().contiguous()
     tg = target.detach().reshape(-1).float().contiguous()
     out = torch.zeros(1, device=output.device)
-    rc = lib.tskd_train_batch_accuracy(
-        ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(tg.data_ptr()),
-        ctypes.c_void_p(out.data_ptr()), ctypes.c_long(lo.numel()), _sp())
-    if rc != 0:
-        raise RuntimeError(f"batch_accuracy kernel failed: hipError {rc}")
+    hip.check(hip.load(hip.TRAIN).tskd_train_batch_accuracy(
+        hip.ptr(lo), hip.ptr(tg), hip.ptr(out), lo.numel(),
+        hip.stream_ptr()), "tskd_train_batch_accuracy")
     return out[0] * 100.0 / batch_size
