@@ -120,14 +120,54 @@ class Consumer:
 
     def poll_samples_sid(self, max_msgs: int = 4096, timeout_ms: int = 0,
                          rank: int = 0, world: int = 1,
-                         max_streams: int = 0):
+                         max_streams: int = 0,
+                         drop_when_full: bool = False):
         """The fully-native serving ingest edge: poll + wire parse + key->
         dense-stream-id mapping + DP shard filter (FNV-1a % world == rank,
         same hash as parallel.shard_for_key) in one C++ pass. Returns
         (sid int32[], chan int32[], value float32[], ts float64[] seconds,
-        new_keys [(key, sid), ...] in sid order)."""
+        new_keys [(key, sid), ...] in admission order).
+
+        A new key takes the lowest sid freed by ``evict_idle``/``release``
+        before the table grows. With the table full and nothing free an
+        unknown key raises ``max_streams exceeded``; ``drop_when_full=True``
+        skips its samples instead and counts them in ``n_rejected()``; the
+        tuple then has a sixth element, the newest event time (seconds)
+        among the samples rejected in this batch (0.0 if none), so that
+        event time passes for the caller even while every arriving patient
+        is turned away."""
         return self._c.poll_samples_sid(max_msgs, timeout_ms, rank, world,
-                                        max_streams)
+                                        max_streams, drop_when_full)
+
+    def evict_idle(self, before_ts: float):
+        """Remove every key whose last-seen event time (seconds, updated at
+        poll time) is ``< before_ts`` and free its sid for reuse. Returns
+        the removed [(key, sid), ...]."""
+        return self._c.evict_idle(float(before_ts))
+
+    def release(self, key: bytes | str) -> int:
+        """Explicit discharge of one key: the freed sid, or -1 if the key
+        is not live."""
+        return self._c.release(key.decode() if isinstance(key, bytes)
+                               else key)
+
+    def n_streams(self) -> int:
+        """Number of live keys."""
+        return self._c.n_streams()
+
+    def sid_high_water(self) -> int:
+        """Slots ever handed out (1 + the highest sid assigned)."""
+        return self._c.sid_high_water()
+
+    def n_rejected(self) -> int:
+        """Samples skipped because the table was full (drop_when_full)."""
+        return self._c.n_rejected()
+
+    def n_admitted(self) -> int:
+        return self._c.n_admitted()
+
+    def n_evicted(self) -> int:
+        return self._c.n_evicted()
 
     def seek(self, topic: str, partition: int, offset: int) -> None:
         self._c.seek(topic, partition, offset)

@@ -18,7 +18,7 @@ import json
 import logging
 import signal
 import time
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -32,8 +32,12 @@ log = logging.getLogger("processStream")
 class ProcessStream:
     def __init__(self, bus: Bus, cfg, max_streams: int = 64,
                  device: str = "cpu", starting: str = "latest",
-                 watermark_s: float = 10.0, out_topic: str = "call-stream"):
+                 watermark_s: float = 10.0, out_topic: str = "call-stream",
+                 evict_idle_s: float = 0.0):
         self.bus = bus
+        # stream lifecycle (opt-in; 0 = off): see FusedServer. When on, the
+        # native slot table is the one allocator (poll_samples_sid).
+        self.evict_idle_s = float(evict_idle_s)
         self.cfg = cfg
         self.out_topic = out_topic
         self.engine = StreamEngine(max_streams, cfg.n_channels,
@@ -50,7 +54,9 @@ class ProcessStream:
         self.max_streams = max_streams
         self.hwm = 0.0
 
-    def _sid(self, pid: str) -> int:
+    def _sid(self, pid: str) -> Optional[int]:
+        if self.evict_idle_s > 0.0:
+            return self.pid_index.get(pid)  # look up only; None if unknown
         if pid not in self.pid_index:
             if len(self.pid_index) >= self.max_streams:
                 raise RuntimeError("max_streams exceeded")
@@ -60,9 +66,43 @@ class ProcessStream:
     def trigger(self) -> int:
         """One micro-batch: drain bus (native C++ wire-format parse), ingest
         events, emit new points."""
+        if self.evict_idle_s > 0.0:
+            emitted = self._emit(*self._drain_lifecycle())
+            # event time, like the watermark; wiped before the next poll.
+            # Only a patient whose newest sample lies behind the processed
+            # grid is evicted: whatever of it is still on its way is then
+            # dropped by the engine as late and cannot reach the wiped slot.
+            self._drop_evicted(self.consumer.evict_idle(min(
+                self.hwm - self.evict_idle_s,
+                self.engine.nproc * self.engine.bucket_s)))
+            return emitted
         keys, _topics, chans, vals, ts_arr = self.consumer.poll_samples(
             max_msgs=65536, timeout_ms=0)
         si = [self._sid(k) for k in keys]
+        return self._emit(si, chans, vals, ts_arr)
+
+    def _drop_evicted(self, pairs) -> None:
+        for key, sid in pairs:
+            if self.pid_index.get(key) == sid:
+                del self.pid_index[key]
+        if pairs:
+            self.engine.reset_streams([sid for _k, sid in pairs])
+
+    def _drain_lifecycle(self):
+        """Drain through the native slot table (the one allocator). Event
+        time also passes on samples rejected for want of a slot."""
+        sa, chans, vals, ts_arr, new_keys, rejected_ts = \
+            self.consumer.poll_samples_sid(
+                max_msgs=65536, timeout_ms=0, max_streams=self.max_streams,
+                drop_when_full=True)
+        self.hwm = max(self.hwm, float(rejected_ts))
+        for k, sid in new_keys:
+            self.pid_index[k] = sid
+        if new_keys:
+            self.engine.admit([sid for _k, sid in new_keys])
+        return sa.tolist(), chans, vals, ts_arr
+
+    def _emit(self, si, chans, vals, ts_arr) -> int:
         n_in = len(si)
         nproc_before = self.engine.nproc
         if n_in:
@@ -126,6 +166,10 @@ def main(argv=None) -> None:
     ap.add_argument("--max-streams", type=int, default=64)
     ap.add_argument("--starting", default="latest",
                     choices=["latest", "earliest"])
+    ap.add_argument("--evict-idle-s", type=float, default=0.0,
+                    help="stream lifecycle: evict a patient silent for more "
+                         "than this many seconds of event time and reuse "
+                         "its ring slot (0 = off)")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="expose Prometheus /metrics on 127.0.0.1:PORT")
     ap.add_argument("--max-triggers", type=int, default=0,
@@ -144,7 +188,8 @@ def main(argv=None) -> None:
     ps = ProcessStream(bus, cfg, max_streams=args.max_streams,
                        device=args.device, starting=args.starting,
                        watermark_s=cfg.watermark_s,
-                       out_topic=args.model_call_topic)
+                       out_topic=args.model_call_topic,
+                       evict_idle_s=args.evict_idle_s)
     trigger_period = cfg.preprocess_trigger_s / args.speed
     stop = []
     signal.signal(signal.SIGTERM, lambda *a: stop.append(1))

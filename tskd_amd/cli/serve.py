@@ -52,7 +52,7 @@ class FusedServer:
                  response_topic: Optional[str] = None,
                  emit_processed: Optional[str] = None,
                  rank: int = 0, world: int = 1,
-                 pipelined: bool = False):
+                 pipelined: bool = False, evict_idle_s: float = 0.0):
         self.cfg = cfg
         self.store = store
         self.ages = ages or AgeTable()
@@ -82,6 +82,22 @@ class FusedServer:
         self.pid_index: Dict[str, int] = {}
         self.pids: list = []
         self.max_streams = max_streams
+        # stream lifecycle (opt-in; 0 = off, ids are then never given back):
+        # a patient silent for more than evict_idle_s of EVENT time is
+        # evicted after a trigger, its ring slot wiped on the GPU and handed
+        # to the next new patient. self.pids is then indexed by slot (None =
+        # free) and predictions are gated per stream (se.stream_ready).
+        # A patient is evicted only once its newest sample also lies behind
+        # the processed grid, so nothing of it that is still on its way (a
+        # chunk the poll thread holds, a late message) can land in the
+        # wiped slot: the engine drops such samples as late.
+        self.evict_idle_s = float(evict_idle_s)
+        self._lifecycle = self.evict_idle_s > 0.0
+        self._slot_version = 0   # bumped whenever pids/pid_index change
+        self._poll_kw = dict(max_msgs=131072, timeout_ms=0, rank=rank,
+                             world=world, max_streams=max_streams)
+        if self._lifecycle:
+            self._poll_kw.update(drop_when_full=True)
         self.hwm = 0.0
         self.watermark_s = cfg.watermark_s
         self.timer = StageTimer("serve")
@@ -119,10 +135,9 @@ class FusedServer:
         def loop():
             try:
                 while not self._poll_stop.is_set():
-                    chunk = self.consumer.poll_samples_sid(
-                        max_msgs=131072, timeout_ms=0, rank=self.rank,
-                        world=self.world, max_streams=self.max_streams)
-                    if len(chunk[0]) or chunk[4]:
+                    chunk = self.consumer.poll_samples_sid(**self._poll_kw)
+                    if len(chunk[0]) or chunk[4] or (
+                            len(chunk) > 5 and chunk[5] > 0.0):
                         with self._poll_lock:
                             self._poll_pending.append(chunk)
                     else:
@@ -145,18 +160,19 @@ class FusedServer:
         """Concatenate the background thread's pending chunks (or poll
         inline when the thread isn't running)."""
         if self._poll_thread is None:
-            return self.consumer.poll_samples_sid(
-                max_msgs=131072, timeout_ms=0, rank=self.rank,
-                world=self.world, max_streams=self.max_streams)
+            return self.consumer.poll_samples_sid(**self._poll_kw)
         if getattr(self, "_poll_error", None) is not None:
             raise RuntimeError("poll thread died") from self._poll_error
         with self._poll_lock:
             chunks, self._poll_pending = self._poll_pending, []
+        # lifecycle chunks carry a sixth element (newest rejected time)
+        tail = (max((c[5] for c in chunks), default=0.0),) \
+            if self._lifecycle else ()
         if not chunks:
             import numpy as _np
             return (_np.empty(0, _np.int32), _np.empty(0, _np.int32),
                     _np.empty(0, _np.float32), _np.empty(0, _np.float64),
-                    [])
+                    []) + tail
         if len(chunks) == 1:
             return chunks[0]
         import numpy as _np
@@ -165,7 +181,7 @@ class FusedServer:
         va = _np.concatenate([c[2] for c in chunks])
         ta = _np.concatenate([c[3] for c in chunks])
         nk = [kv for c in chunks for kv in c[4]]
-        return sa, ca, va, ta, nk
+        return (sa, ca, va, ta, nk) + tail
 
     def _stamp(self, key: Optional[str], t0: float) -> float:
         import time as _time
@@ -206,12 +222,50 @@ class FusedServer:
         densely in first-seen order and filter by the same FNV-1a shard)."""
         if self.world > 1 and shard_for_key(pid, self.world) != self.rank:
             return None  # another rank's patient
+        if self._lifecycle:
+            # the native slot table is the only allocator: look up only
+            return self.pid_index.get(pid)
         if pid not in self.pid_index:
             if len(self.pid_index) >= self.max_streams:
                 raise RuntimeError("max_streams exceeded")
             self.pid_index[pid] = len(self.pid_index)
             self.pids.append(pid)
+            self._slot_version += 1
         return self.pid_index[pid]
+
+    def _drop_evicted(self, pairs) -> None:
+        """Forget evicted (key, sid) pairs and wipe their ring slots (one
+        reset launch) so the next occupant inherits nothing."""
+        if not pairs:
+            return
+        for key, sid in pairs:
+            if self.pid_index.get(key) == sid:
+                del self.pid_index[key]
+            if sid < len(self.pids) and self.pids[sid] == key:
+                self.pids[sid] = None
+        self._slot_version += 1
+        self.se.reset_streams([sid for _k, sid in pairs])
+
+    def _admit(self, new_keys, sa, ta) -> None:
+        """Admit the trigger's new patients: each one's warm-up counts from
+        the bucket of its first sample that the engine will accept (one
+        behind the processed grid is dropped as late), never from before
+        the current grid point."""
+        import numpy as _np
+        live = ta >= self.se.nproc * self.se.bucket_s
+        first = _np.full(self.se.S, _np.inf)
+        _np.minimum.at(first, sa[live], ta[live])
+        sids = _np.asarray([sid for _k, sid in new_keys], dtype=_np.int64)
+        t_first = first[sids]
+        t_first[~_np.isfinite(t_first)] = 0.0   # no live sample: from now
+        self.se.admit(sids, at=(t_first // self.se.bucket_s).astype(
+            _np.int64))
+
+    def _update_gauges(self) -> None:
+        c = self.consumer
+        self.timer.gauges.update(
+            active=c.n_streams(), admitted_total=c.n_admitted(),
+            evicted_total=c.n_evicted(), rejected_total=c.n_rejected())
 
     def trigger(self) -> int:
         """Drain bus -> ingest -> fused preprocess+infer -> store."""
@@ -221,11 +275,27 @@ class FusedServer:
             # native edge: poll + wire parse + key->sid + shard filter in
             # one C++ pass (no per-message Python — VERDICT r1 item #3);
             # with the poll thread running this just swaps buffers
-            sa, ca, va, ta, new_keys = self._take_polled()
+            sa, ca, va, ta, new_keys, *rejected_ts = self._take_polled()
             t0 = self._stamp("poll", t0)
-            for k, sid in new_keys:
-                self.pid_index[k] = sid
-                self.pids.append(k)
+            if self._lifecycle:
+                # event time passes even while every arriving patient is
+                # turned away (a ward turning over all at once would
+                # otherwise never reach the idle cut)
+                for r in rejected_ts:
+                    self.hwm = max(self.hwm, float(r))
+                for k, sid in new_keys:
+                    if sid >= len(self.pids):
+                        self.pids.extend([None] * (sid + 1 - len(self.pids)))
+                    self.pid_index[k] = sid
+                    self.pids[sid] = k
+                if new_keys:
+                    self._admit(new_keys, sa, ta)
+            else:
+                for k, sid in new_keys:
+                    self.pid_index[k] = sid
+                    self.pids.append(k)
+            if new_keys:
+                self._slot_version += 1
             self.flush()  # pipelined: persist trigger T-1 AFTER the poll
                           # overlapped its GPU tail (no-op otherwise)
             if len(ta):
@@ -263,53 +333,83 @@ class FusedServer:
                                               f"{pid}_{c}",
                                               _json.dumps(rows[c]),
                                               ts_us=int(self.hwm * 1e6))
-            if np_new <= 0 or not self.se.ready or not self.pids:
-                return 0
-            dtype = torch.bfloat16 if self.device != "cpu" else torch.float32
-            n_active = len(self.pids)
-            # cached device buffers: the age column only changes when the
-            # patient set grows, and the gather kernel overwrites every
-            # window element — rebuilding these per trigger cost ~13 ms of
-            # Python at 16k live patients (serving_latency_big.json)
-            if getattr(self, "_age_n", 0) != n_active:
-                self._age_dev = torch.tensor(
-                    [[self.ages.get(p)] for p in self.pids],
-                    device=self.se.device)
-                self._age_n = n_active
-            if getattr(self, "_win_buf", None) is None or \
-                    self._win_buf.dtype != dtype:
-                tl = self.device != "cpu"
-                shape = (self.se.S, 1, self.se.model_win, self.se.C) if tl \
-                    else (self.se.S, 1, self.se.C, self.se.model_win)
-                self._win_buf = torch.zeros(shape, dtype=dtype,
-                                            device=self.se.device)
-            w = self.se.windows(batch=1, stride=12, dtype=dtype,
-                                timelast=self.device != "cpu",
-                                out=self._win_buf)
-            age = self._age_dev
-            probs_all = self.me.forward(w[:n_active].contiguous()
-                                        if n_active < self.se.S else w,
-                                        age, apply_sigmoid=True)
-            probs = probs_all.reshape(-1)[:n_active]
-            t_us = int(self.hwm * 1e6)
-            if self.world > 1:
-                # every rank sees the full per-trigger prediction set
-                # (monitoring/router hook) — tiny direct all-gather on xGMI
-                pad = torch.zeros(self.max_streams, device=probs.device)
-                pad[:n_active] = probs
-                self.last_gathered = all_gather_predictions(pad)
-            t0 = self._stamp("model", t0)
-            if self.pipelined:
-                # defer the device sync: persist at the next trigger start,
-                # after the bus poll has overlapped this trigger's GPU work
-                self._pending = (probs, t_us, list(self.pids))
-            else:
-                self._persist(probs, t_us, self.pids)
-            self._stamp("persist", t0)
-            self.timer.add_items(n_active)
-            return n_active
+            n = self._score(np_new, t0)
+            if self._lifecycle:
+                # event time, like the watermark: --speed-invariant. The
+                # slots are wiped in THIS trigger, before the next poll is
+                # consumed.
+                self._drop_evicted(self.consumer.evict_idle(min(
+                    self.hwm - self.evict_idle_s,
+                    self.se.nproc * self.se.bucket_s)))
+                self._update_gauges()
+            return n
 
-    def _persist(self, probs, t_us: int, pids) -> None:
+    def _score(self, np_new: int, t0: float) -> int:
+        """Score the latest window of every slot in use and persist the
+        predictions of the live, ready streams; returns their number."""
+        if np_new <= 0 or not self.pids:
+            return 0
+        mask = None
+        if self._lifecycle:
+            ready = self.se.stream_ready()
+            mask = [p is not None and bool(ready[i])
+                    for i, p in enumerate(self.pids)]
+            if not any(mask):
+                return 0
+        elif not self.se.ready:
+            return 0
+        dtype = torch.bfloat16 if self.device != "cpu" else torch.float32
+        n_active = len(self.pids)
+        # cached device buffers: the age column only changes when the
+        # slot table does (version counter), and the gather overwrites every
+        # window element — rebuilding these per trigger cost ~13 ms of
+        # Python at 16k live patients (serving_latency_big.json)
+        if getattr(self, "_age_ver", -1) != self._slot_version:
+            self._age_dev = torch.tensor(
+                [[self.ages.get(p) if p is not None else 65.0]
+                 for p in self.pids], device=self.se.device)
+            self._age_ver = self._slot_version
+        if getattr(self, "_win_buf", None) is None or \
+                self._win_buf.dtype != dtype:
+            tl = self.device != "cpu"
+            shape = (self.se.S, 1, self.se.model_win, self.se.C) if tl \
+                else (self.se.S, 1, self.se.C, self.se.model_win)
+            self._win_buf = torch.zeros(shape, dtype=dtype,
+                                        device=self.se.device)
+        w = self.se.windows(batch=1, stride=12, dtype=dtype,
+                            timelast=self.device != "cpu",
+                            out=self._win_buf)
+        age = self._age_dev
+        probs_all = self.me.forward(w[:n_active].contiguous()
+                                    if n_active < self.se.S else w,
+                                    age, apply_sigmoid=True)
+        probs = probs_all.reshape(-1)[:n_active]
+        t_us = int(self.hwm * 1e6)
+        if self.world > 1:
+            # every rank sees the full per-trigger prediction set
+            # (monitoring/router hook) — tiny direct all-gather on xGMI
+            pad = torch.zeros(self.max_streams, device=probs.device)
+            pad[:n_active] = probs
+            self.last_gathered = all_gather_predictions(pad)
+        t0 = self._stamp("model", t0)
+        if self.pipelined:
+            # defer the device sync: persist at the next trigger start,
+            # after the bus poll has overlapped this trigger's GPU work
+            self._pending = (probs, t_us, list(self.pids), mask)
+        else:
+            self._persist(probs, t_us, self.pids, mask)
+        self._stamp("persist", t0)
+        n_scored = n_active if mask is None else sum(mask)
+        self.timer.add_items(n_scored)
+        return n_scored
+
+    def _persist(self, probs, t_us: int, pids, mask=None) -> None:
+        if mask is not None:
+            # lifecycle: only live, ready slots are persisted and published
+            keep = [i for i, m in enumerate(mask) if m]
+            probs = probs.reshape(-1)[:len(pids)][
+                torch.tensor(keep, dtype=torch.long, device=probs.device)]
+            pids = [pids[i] for i in keep]
         n = len(pids)
         if self.store is not None:
             # the mmap store is multi-process safe: each rank persists
@@ -328,9 +428,9 @@ class FusedServer:
         """Persist the deferred trigger (pipelined mode; call on shutdown
         or whenever durability must catch up to compute)."""
         if self._pending is not None:
-            probs, t_us, pids = self._pending
+            probs, t_us, pids, mask = self._pending
             self._pending = None
-            self._persist(probs, t_us, pids)
+            self._persist(probs, t_us, pids, mask)
 
 
 
@@ -390,6 +490,11 @@ def main(argv=None) -> None:
     ap.add_argument("--pipelined", action="store_true",
                     help="overlap the bus poll of trigger T+1 with trigger "
                          "T's GPU work (persistence lags one trigger)")
+    ap.add_argument("--evict-idle-s", type=float, default=0.0,
+                    help="stream lifecycle: evict a patient silent for more "
+                         "than this many seconds of event time and reuse "
+                         "its ring slot (0 = off: ids are never given back "
+                         "and patient --max-streams+1 is fatal)")
     ap.add_argument("--poll-thread", action="store_true",
                     help="drain+parse the bus continuously on a background "
                          "thread (C++ releases the GIL); the trigger only "
@@ -413,7 +518,8 @@ def main(argv=None) -> None:
                       starting=args.starting,
                       response_topic=args.model_response_topic,
                       emit_processed=args.emit_processed,
-                      rank=rank, world=world, pipelined=args.pipelined)
+                      rank=rank, world=world, pipelined=args.pipelined,
+                      evict_idle_s=args.evict_idle_s)
     if args.poll_thread:
         srv.start_poll_thread()
     if args.hot_reload and args.model_path:

@@ -79,6 +79,9 @@ class StreamEngine:
         self._cm_cache = {}  # chan_map tuple -> int32 device tensor
         self._warned_partial = False
         self._forced_ready = False
+        # stream lifecycle: grid point at which each slot's CURRENT occupant
+        # was admitted (0 = since the engine began; see admit/stream_ready)
+        self.born = np.zeros(self.S, dtype=np.int64)
         if self._gpu:
             hip.load(hip.PREPROC)  # fail here, not at the first launch
 
@@ -458,6 +461,73 @@ class StreamEngine:
         behave the same as zero-based replay times)."""
         return self._forced_ready or \
             self.nproc - self._origin_nproc >= self.model_win
+
+    # --------------------------------------------------------------- lifecycle
+    def _check_sids(self, sids) -> np.ndarray:
+        """``sids`` as an int64 array, every id in [0, S) — else ValueError
+        (an out-of-range id must never reach a kernel)."""
+        ids = np.asarray(
+            sids.cpu() if isinstance(sids, torch.Tensor) else sids)
+        if ids.size == 0:
+            return np.empty(0, dtype=np.int64)
+        if ids.dtype.kind not in "iu":
+            raise ValueError(f"stream ids must be integers, got {ids.dtype}")
+        ids = ids.astype(np.int64).reshape(-1)
+        if ids.min() < 0 or ids.max() >= self.S:
+            raise ValueError(
+                f"stream id out of range [0, {self.S}): "
+                f"{int(ids.min())}..{int(ids.max())}")
+        return ids
+
+    def reset_streams(self, sids) -> None:
+        """Return the listed stream slots to the never-used state: bucket
+        sums, bucket counts and processed points 0, fill carry NaN — what a
+        slot holds before any patient has used it, so the next occupant
+        inherits nothing. Duplicates are harmless; an empty list is a no-op.
+        Reads no ring position (legal between graph replays). Does not
+        touch ``born``: a slot may sit free long before it is re-admitted."""
+        ids = self._check_sids(sids)
+        if ids.size == 0:
+            return
+        if self._gpu:
+            dids = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_reset_streams(
+                hip.ptr(dids), int(ids.size), hip.ptr(self.bsum),
+                hip.ptr(self.bcnt), hip.ptr(self.proc),
+                hip.ptr(self.last_val), self.S, self.C, self.G, self._bst,
+                hip.stream_ptr()), "tskd_preproc_reset_streams")
+        else:
+            idx = torch.from_numpy(np.unique(ids))
+            self.bsum[idx] = 0
+            self.bcnt[idx] = 0
+            self.proc[idx] = 0
+            self.last_val[idx] = float("nan")
+
+    def admit(self, sids, at=None) -> None:
+        """A new occupant takes the listed slots now: ``stream_ready`` for
+        them counts a full model window from the current grid point.
+        ``at``: optional per-slot grid point (the bucket of the occupant's
+        first sample) to count from instead when it lies AHEAD of the
+        current one — the warm-up then holds 120 points of the occupant's
+        own data however long the grid stood still before it arrived."""
+        ids = self._check_sids(sids)
+        if ids.size:
+            born = np.full(ids.shape, self.nproc, dtype=np.int64)
+            if at is not None:
+                born = np.maximum(born, np.asarray(at, dtype=np.int64))
+            self.born[ids] = born
+
+    def stream_ready(self, sids=None) -> np.ndarray:
+        """Per-stream ``ready``: bool mask over ``sids`` (all S streams when
+        None) — a full model window has been produced since the stream's
+        occupant was admitted (the reference's per-key "waiting until there
+        are 120 signals" gate, predictStream.py:117-127). With ``admit``
+        never called every entry equals ``ready``."""
+        born = self.born if sids is None else self.born[self._check_sids(sids)]
+        if self._forced_ready:
+            return np.ones(born.shape, dtype=bool)
+        return self.nproc - np.maximum(born, self._origin_nproc) \
+            >= self.model_win
 
     def force_ready(self) -> None:
         """Declare the engine warm (steady-state serving): benchmarks that

@@ -15,11 +15,19 @@ from collections import deque
 from typing import Dict, Optional
 
 
+STREAM_STATES = ("active", "admitted_total", "evicted_total",
+                 "rejected_total")
+
+
 class StageTimer:
     """Rolling latency/throughput stats for one pipeline stage."""
 
-    def __init__(self, name: str, window: int = 512):
+    def __init__(self, name: str, window: int = 512,
+                 gauges: Optional[Dict[str, float]] = None):
         self.name = name
+        # optional stream-lifecycle gauges/counters of this stage: any of
+        # "active", "admitted_total", "evicted_total", "rejected_total"
+        self.gauges: Dict[str, float] = dict(gauges or {})
         self.lat = deque(maxlen=window)
         self.items = 0
         self.calls = 0
@@ -46,7 +54,7 @@ class StageTimer:
 
     def snapshot(self) -> Dict:
         elapsed = max(time.time() - self.t_start, 1e-9)
-        return {
+        snap = {
             "stage": self.name,
             "calls": self.calls,
             "items": self.items,
@@ -55,6 +63,9 @@ class StageTimer:
             "p99_ms": self._pct(0.99) * 1e3,
             "last_ms": (self.lat[-1] * 1e3) if self.lat else 0.0,
         }
+        if self.gauges:
+            snap["streams"] = dict(self.gauges)
+        return snap
 
     def log_line(self) -> str:
         return json.dumps(self.snapshot())
@@ -89,6 +100,7 @@ def prometheus_text(timers) -> str:
         "# HELP tskd_stage_latency_ms Stage latency quantiles (rolling).",
         "# TYPE tskd_stage_latency_ms gauge",
     ]
+    timers = list(timers)
     for t in timers:
         snap = t.snapshot()
         lbl = f'stage="{snap["stage"]}"'
@@ -97,4 +109,16 @@ def prometheus_text(timers) -> str:
         for q in ("p50", "p99"):
             lines.append(f'tskd_stage_latency_ms{{{lbl},quantile="{q}"}} '
                          f'{snap[q + "_ms"]:.6f}')
+    gauged = [t for t in timers if getattr(t, "gauges", None)]
+    if gauged:
+        lines.append("# HELP tskd_streams Stream slots: live now, and "
+                     "admitted/evicted/rejected since start.")
+        lines.append("# TYPE tskd_streams gauge")
+    for t in gauged:
+        for state in STREAM_STATES:
+            if state in t.gauges:
+                v = t.gauges[state]
+                v = int(v) if float(v).is_integer() else float(v)
+                lines.append(f'tskd_streams{{stage="{t.name}",'
+                             f'state="{state}"}} {v}')
     return "\n".join(lines) + "\n"

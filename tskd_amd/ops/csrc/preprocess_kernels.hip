@@ -245,6 +245,59 @@ __global__ void clear_buckets_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// 1c. Stream reset: return the listed stream slots to the never-used state
+//     (bucket sums/counts and processed points 0, fill carry NaN) so that a
+//     slot given up by one patient carries nothing over to the next.
+// ---------------------------------------------------------------------------
+// A stream owns up to three contiguous float regions of per-stream length
+// len[r] at base[r] + sid * len[r]: the packed (sum,cnt) pairs (2*C*G) and
+// proc (C*G), or bsum, bcnt and proc (C*G each). blockIdx.y strides over the
+// id list, blockIdx.x over the stream's store units; a region whose length is
+// a multiple of 4 floats (and whose base is 16 B-aligned — the launcher
+// checks) is written with 16 B stores, any other with dword stores. Reads no
+// ring position, so it may run between graph replays.
+struct ResetRegions {
+    float* base[3];
+    int len[3];     // floats per stream
+    int vec[3];     // 1: 16 B stores
+    int units[3];   // store units per stream (len/4 or len; 0 = unused)
+};
+
+__global__ __launch_bounds__(256) void reset_streams_kernel(
+    const int* __restrict__ sids, int n, ResetRegions rg,
+    float* __restrict__ last_val, int S, int C)
+{
+    const int total = rg.units[0] + rg.units[1] + rg.units[2];
+    const f32x4_ z4 = {0.f, 0.f, 0.f, 0.f};
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const int s = sids[k];
+        if ((unsigned)s >= (unsigned)S) continue;  // host range-checks too
+        // 64-bit stride: total may be close to 2^31 (the launcher's bound)
+        for (long u = (long)blockIdx.x * blockDim.x + threadIdx.x; u < total;
+             u += (long)gridDim.x * blockDim.x) {
+            // constant indices only: the region table stays in scalar
+            // registers (a lane-indexed table would go to scratch)
+            float* base = rg.base[0];
+            int len = rg.len[0], vec = rg.vec[0], v = (int)u;
+            if (v >= rg.units[0]) {
+                v -= rg.units[0];
+                base = rg.base[1]; len = rg.len[1]; vec = rg.vec[1];
+                if (v >= rg.units[1]) {
+                    v -= rg.units[1];
+                    base = rg.base[2]; len = rg.len[2]; vec = rg.vec[2];
+                }
+            }
+            float* p = base + (long)s * len;
+            if (vec) ((f32x4_*)p)[v] = z4;
+            else p[v] = 0.f;
+        }
+        if (blockIdx.x == 0)
+            for (int c = threadIdx.x; c < C; c += blockDim.x)
+                last_val[(long)s * C + c] = NAN;
+    }
+}
+
+// ---------------------------------------------------------------------------
 // 2. Sliding-window average + ffill/bfill/zero-fill
 //    Processes proc grid points [phead, phead+np): window starting at grid j
 //    averages buckets [j, j+win_buckets). One thread per (s, c): the fill is
@@ -667,6 +720,41 @@ int tskd_preproc_clear_buckets(float* bsum, float* bcnt, int S, int C, int G,
     hipLaunchKernelGGL(clear_buckets_kernel, dim3(grid_for(n, 256)), dim3(256),
                        0, (hipStream_t)stream, bsum, bcnt, S, C, G, head, nb,
                        bst);
+    return (int)hipGetLastError();
+}
+
+int tskd_preproc_reset_streams(const int* sids, int n, float* bsum,
+                               float* bcnt, float* proc, float* last_val,
+                               int S, int C, int G, int bst, void* stream) {
+    if (n <= 0) return 0;
+    const long cg = (long)C * G;
+    if (S <= 0 || cg <= 0 || 3 * cg > 0x7fffffffL) return -4;
+    if (bst == 2 && bcnt != bsum + 1) return -5;  // not (sum,cnt) pairs
+    ResetRegions rg = {};
+    int nreg = 0;
+    auto add = [&](float* base, long len) {
+        rg.base[nreg] = base;
+        rg.len[nreg] = (int)len;
+        rg.vec[nreg] = len % 4 == 0 && ((size_t)base & 15) == 0;
+        rg.units[nreg] = (int)(rg.vec[nreg] ? len / 4 : len);
+        ++nreg;
+    };
+    if (bst == 2) {
+        add(bsum, 2 * cg);  // one contiguous run of (sum,cnt) pairs
+    } else {
+        add(bsum, cg);
+        add(bcnt, cg);
+    }
+    add(proc, cg);
+    const int total = rg.units[0] + rg.units[1] + rg.units[2];
+    // ~4096 blocks over (ids x chunks): enough to fill the chip for one
+    // stream, no more launch tail than that for thousands
+    const int gy = n < 4096 ? n : 4096;
+    int gx = (total + 255) / 256;
+    if (gx > 4096 / gy) gx = 4096 / gy;
+    if (gx < 1) gx = 1;
+    hipLaunchKernelGGL(reset_streams_kernel, dim3(gx, gy), dim3(256), 0,
+                       (hipStream_t)stream, sids, n, rg, last_val, S, C);
     return (int)hipGetLastError();
 }
 
