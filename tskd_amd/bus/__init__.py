@@ -151,6 +151,23 @@ class Consumer:
         return self._c.release(key.decode() if isinstance(key, bytes)
                                else key)
 
+    def slot_table(self):
+        """The key -> sid table as it stands: ([(key, sid, last_seen), ...],
+        high_water). With ``positions()`` it is what a successor needs to
+        take over this consumer's patients under the same ids."""
+        entries, high_water = self._c.slot_table()
+        return list(entries), high_water
+
+    def restore_slots(self, entries, high_water: int) -> None:
+        """Rebuild the slot table from a ``slot_table()`` of an earlier
+        consumer: every sid below ``high_water`` that no entry uses is free,
+        so new keys take the same lowest-free sids as the original. Legal
+        only before the first poll (RuntimeError after it); a duplicate key
+        or sid, or a sid outside [0, high_water), raises ValueError."""
+        self._c.restore_slots(
+            [(k.decode() if isinstance(k, bytes) else str(k), int(s),
+              float(t)) for k, s, t in entries], int(high_water))
+
     def n_streams(self) -> int:
         """Number of live keys."""
         return self._c.n_streams()

@@ -33,7 +33,7 @@ import torch
 
 from tskd_amd.bus import Bus, Consumer, Producer
 from tskd_amd.config import get_global_config
-from tskd_amd.engine import StreamEngine
+from tskd_amd.engine import EngineSnapshot, StreamEngine
 from tskd_amd.metrics import StageTimer
 from tskd_amd.models import build_model
 from tskd_amd.ops import MyCNNEngine
@@ -52,8 +52,15 @@ class FusedServer:
                  response_topic: Optional[str] = None,
                  emit_processed: Optional[str] = None,
                  rank: int = 0, world: int = 1,
-                 pipelined: bool = False, evict_idle_s: float = 0.0):
+                 pipelined: bool = False, evict_idle_s: float = 0.0,
+                 state_path: Optional[str] = None, snapshot_every: int = 1):
         self.cfg = cfg
+        # warm restart: every snapshot_every-th trigger ends by writing ONE
+        # file (save_state) that a successor process resumes from
+        # (load_state); None = off
+        self.state_path = state_path
+        self.snapshot_every = max(1, int(snapshot_every))
+        self._n_triggers = 0
         self.store = store
         self.ages = ages or AgeTable()
         self.rank, self.world = rank, world
@@ -342,6 +349,10 @@ class FusedServer:
                     self.hwm - self.evict_idle_s,
                     self.se.nproc * self.se.bucket_s)))
                 self._update_gauges()
+            self._n_triggers += 1
+            if self.state_path and \
+                    self._n_triggers % self.snapshot_every == 0:
+                self.save_state(self.state_path)
             return n
 
     def _score(self, np_new: int, t0: float) -> int:
@@ -432,6 +443,88 @@ class FusedServer:
             self._pending = None
             self._persist(probs, t_us, pids, mask)
 
+    # ------------------------------------------------------------ warm restart
+    def save_state(self, path: Optional[str] = None) -> None:
+        """Write everything a successor needs to continue from this trigger
+        into ONE file, replaced atomically: the live slots' ring tails
+        (StreamEngine.snapshot) and, beside them, the bus positions, the
+        slot table, the event-time high-water mark, rank/world and the model
+        variant. Offsets, slot ids and ring contents can therefore never
+        disagree. A deferred pipelined trigger is persisted first. Ring
+        state is exactly-once; predictions made after the last snapshot are
+        written again by the successor with the same (pid, t_us, risk)."""
+        if self._poll_thread is not None:
+            raise RuntimeError("save_state with the poll thread running: "
+                               "bus positions run ahead of the rings")
+        self.flush()
+        entries, high_water = self.consumer.slot_table()
+        snap = self.se.snapshot(sorted(sid for _k, sid, _t in entries))
+        snap.save(path or self.state_path, extra={
+            "positions": self.consumer.positions(),
+            "slots": [[k, sid, t] for k, sid, t in entries],
+            "high_water": high_water, "hwm": self.hwm,
+            "rank": self.rank, "world": self.world,
+            "model": type(self.me.model).__name__})
+
+    def load_state(self, path: Optional[str] = None) -> bool:
+        """Resume from a save_state file: restore the rings, the slot table
+        (engine and consumer), ``hwm`` and the bus positions, so the next
+        trigger consumes exactly what the writer had not yet put into the
+        snapshot. Call before the first trigger. A file that is corrupt, of
+        another rank/world or that does not fit this server is refused: one
+        error line, ``restore_failed`` + 1, and a cold start as without a
+        file (returns False)."""
+        path = path or self.state_path
+        try:
+            snap, extra = EngineSnapshot.load(path)
+            if (extra["rank"], extra["world"]) != (self.rank, self.world):
+                raise ValueError(
+                    f"written by rank {extra['rank']} of {extra['world']}, "
+                    f"this is rank {self.rank} of {self.world}")
+            slots = [(str(k), int(sid), float(t))
+                     for k, sid, t in extra["slots"]]
+            high_water = int(extra["high_water"])
+            positions = {str(k): int(v)
+                         for k, v in extra["positions"].items()}
+            hwm = float(extra["hwm"])
+            if high_water > self.max_streams:
+                raise ValueError(f"{high_water} slots in the file, "
+                                 f"max_streams={self.max_streams}")
+            if not self._lifecycle and len(slots) != high_water:
+                raise ValueError("the file has free slots (written with "
+                                 "--evict-idle-s), this server never "
+                                 "reuses a slot")
+            if sorted(sid for _k, sid, _t in slots) != snap.sids.tolist() \
+                    or len({k for k, _s, _t in slots}) != len(slots) \
+                    or any(not 0 <= sid < high_water for _k, sid, _t in slots):
+                raise ValueError("slot table and ring snapshot disagree")
+            self.se.restore(snap)  # checks everything before it writes
+        except (OSError, ValueError, KeyError, TypeError) as e:
+            log.error("state file %s refused (%s): cold start", path, e)
+            self.timer.gauges["restore_failed"] = \
+                self.timer.gauges.get("restore_failed", 0) + 1
+            return False
+        if extra.get("model") != type(self.me.model).__name__:
+            log.warning("state written under model %s, serving %s",
+                        extra.get("model"), type(self.me.model).__name__)
+        self.consumer.restore_slots(slots, high_water)
+        for key, off in positions.items():
+            topic, _, part = key.rpartition("/")
+            self.consumer.seek(topic, int(part), off)
+        self.pids = [None] * high_water
+        self.pid_index = {}
+        for k, sid, _t in slots:
+            self.pids[sid] = k
+            self.pid_index[k] = sid
+        self.hwm = hwm
+        self._slot_version += 1
+        log.info("resumed %d streams at grid point %d from %s", len(slots),
+                 self.se.nproc, path)
+        return True
+
+
+def state_file(state_dir: str, rank: int, world: int) -> str:
+    return os.path.join(state_dir, f"serve-rank{rank}of{world}.snap")
 
 
 def start_metrics_server(timers, port: int):
@@ -500,7 +593,22 @@ def main(argv=None) -> None:
                          "thread (C++ releases the GIL); the trigger only "
                          "ingests/scores — removes the poll from the "
                          "latency path at saturating rates")
+    ap.add_argument("--state-dir", default=None, metavar="DIR",
+                    help="warm restart: resume from DIR/serve-rank{r}of{w}"
+                         ".snap when it exists (ring tails, slot table and "
+                         "bus offsets in one atomically replaced file) and "
+                         "keep it up to date; a file that is refused means "
+                         "a cold start")
+    ap.add_argument("--snapshot-every", type=int, default=1, metavar="N",
+                    help="with --state-dir: write the state file every N "
+                         "triggers (and once more on SIGTERM)")
     args = ap.parse_args(argv)
+    if args.state_dir and args.poll_thread:
+        ap.error("--state-dir cannot be combined with --poll-thread: the "
+                 "poll thread owns the consumer, so the bus positions run "
+                 "ahead of the rings a snapshot would pair them with")
+    if args.snapshot_every < 1:
+        ap.error("--snapshot-every must be at least 1")
 
     rank, world = init_distributed()
     from tskd_amd.cli.predictstream import load_model_for_serving
@@ -519,7 +627,13 @@ def main(argv=None) -> None:
                       response_topic=args.model_response_topic,
                       emit_processed=args.emit_processed,
                       rank=rank, world=world, pipelined=args.pipelined,
-                      evict_idle_s=args.evict_idle_s)
+                      evict_idle_s=args.evict_idle_s,
+                      snapshot_every=args.snapshot_every)
+    if args.state_dir:
+        os.makedirs(args.state_dir, exist_ok=True)
+        srv.state_path = state_file(args.state_dir, rank, world)
+        if os.path.exists(srv.state_path):
+            srv.load_state()
     if args.poll_thread:
         srv.start_poll_thread()
     if args.hot_reload and args.model_path:
@@ -547,6 +661,8 @@ def main(argv=None) -> None:
         time.sleep(max(0.0, period - (time.time() - t0)))
     srv.stop_poll_thread()
     srv.flush()  # pipelined mode: persist the final deferred trigger
+    if srv.state_path:
+        srv.save_state()  # SIGTERM / --max-triggers: nothing to replay
 
 
 if __name__ == "__main__":

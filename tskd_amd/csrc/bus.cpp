@@ -25,6 +25,7 @@
 #include <set>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include <dirent.h>
@@ -487,6 +488,7 @@ public:
         // release the GIL for the whole scan so a background poll thread
         // (serve.py start_poll_thread) truly overlaps Python/GPU work
         py::gil_scoped_release rel_scan;
+        polled_.store(true, std::memory_order_relaxed);
         std::vector<Message> out;
         const int64_t deadline = now_us() + (int64_t)timeout_ms * 1000;
         while (true) {
@@ -657,6 +659,50 @@ public:
         return sid;
     }
 
+    // The slot table as it stands: ([(key, sid, last_seen), ...], high
+    // water) — what restore_slots needs to rebuild it in another process.
+    py::tuple slot_table() {
+        std::lock_guard<std::mutex> g(slot_mtx_);
+        std::vector<std::tuple<std::string, int, double>> out;
+        out.reserve(slots_.size());
+        for (auto& [key, slot] : slots_)
+            out.emplace_back(key, slot.sid, slot.last_seen);
+        return py::make_tuple(out, high_water_);
+    }
+
+    // Rebuild slots_, free_ and high_water_ from a slot_table() taken by an
+    // earlier consumer (warm restart): every sid below high water that no
+    // entry uses is free, so new keys take the same lowest-free sids the
+    // original would have handed out. Only before the first poll — later the
+    // table already maps keys of its own. Counters start again from zero.
+    void restore_slots(
+        const std::vector<std::tuple<std::string, int, double>>& entries,
+        int high_water) {
+        std::lock_guard<std::mutex> g(slot_mtx_);
+        if (polled_.load(std::memory_order_relaxed) || !slots_.empty() ||
+            high_water_ != 0)
+            throw std::runtime_error(
+                "restore_slots: only before the first poll");
+        std::map<std::string, Slot> slots;
+        std::set<int> used;
+        for (auto& [key, sid, last_seen] : entries) {
+            if (sid < 0 || sid >= high_water)
+                throw std::invalid_argument(
+                    "restore_slots: sid outside [0, high_water): " + key);
+            if (!used.insert(sid).second)
+                throw std::invalid_argument(
+                    "restore_slots: duplicate sid " + std::to_string(sid));
+            if (!slots.emplace(key, Slot{sid, last_seen}).second)
+                throw std::invalid_argument(
+                    "restore_slots: duplicate key " + key);
+        }
+        slots_ = std::move(slots);
+        free_.clear();
+        for (int sid = 0; sid < high_water; ++sid)
+            if (!used.count(sid)) free_.insert(sid);
+        high_water_ = high_water;
+    }
+
     int n_streams() {  // live keys
         std::lock_guard<std::mutex> g(slot_mtx_);
         return (int)slots_.size();
@@ -701,6 +747,7 @@ private:
             }
         }
     }
+    std::atomic<bool> polled_{false};  // restore_slots is legal until set
     std::mutex slot_mtx_;  // slots_, free_, counters (see poll_samples_sid)
     std::map<std::string, Slot> slots_;  // key -> stream slot (serving)
     std::set<int> free_;                 // slots handed back, lowest first
@@ -758,6 +805,9 @@ PYBIND11_MODULE(_tskd_bus, m) {
              py::arg("drop_when_full") = false)
         .def("evict_idle", &Consumer::evict_idle, py::arg("before_ts"))
         .def("release", &Consumer::release, py::arg("key"))
+        .def("slot_table", &Consumer::slot_table)
+        .def("restore_slots", &Consumer::restore_slots, py::arg("entries"),
+             py::arg("high_water"))
         .def("n_streams", &Consumer::n_streams)
         .def("sid_high_water", &Consumer::sid_high_water)
         .def("n_rejected", &Consumer::n_rejected)

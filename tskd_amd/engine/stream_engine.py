@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from tskd_amd.engine import windowing as W
+from tskd_amd.engine.snapshot import GEOMETRY, EngineSnapshot
 from tskd_amd.ops import hip
 
 
@@ -82,6 +83,10 @@ class StreamEngine:
         # stream lifecycle: grid point at which each slot's CURRENT occupant
         # was admitted (0 = since the engine began; see admit/stream_ready)
         self.born = np.zeros(self.S, dtype=np.int64)
+        # warm restart: processed points below this grid point were not
+        # carried over by restore() (0 on an engine that was never restored)
+        self._proc_floor = 0
+        self._snap_dev = self._snap_host = None  # reused staging buffers
         if self._gpu:
             hip.load(hip.PREPROC)  # fail here, not at the first launch
 
@@ -399,6 +404,7 @@ class StreamEngine:
             f"windows(batch={B}, stride={stride}) reaches back "
             f"{(B - 1) * stride + WIN} grid points but the ring holds only "
             f"G={self.G} — older slots are already overwritten")
+        self._check_floor((B - 1) * stride + WIN)
         shape = (self.S, B, WIN, self.C) if timelast \
             else (self.S, B, self.C, WIN)
         provided = out is not None
@@ -449,6 +455,7 @@ class StreamEngine:
         dtype=bf16, timelast=True)`` + ``model_engine.forward``; capture-
         safe (ring position from the device state block when one is set)."""
         assert self._gpu and self.model_win == 120
+        self._check_floor(self.model_win)
         return model_engine.score_ring(
             self.proc, self.G, self.nproc, self._dstate_ptr(),
             self._dstate_gather_extra, age, apply_sigmoid)
@@ -535,6 +542,171 @@ class StreamEngine:
         skip the reference's ~13-minute first-window ramp (windows shorter
         than 600 s are zero-padded, exactly as mid-history windows are)."""
         self._forced_ready = True
+
+    # ------------------------------------------------------------ warm restart
+    def _geometry(self) -> dict:
+        return {"C": self.C, "fs": self.fs, "bucket_s": self.bucket_s,
+                "win_buckets": self.win_buckets, "model_win": self.model_win}
+
+    def _check_floor(self, reach: int) -> None:
+        """A gather reaching ``reach`` grid points back from the latest one
+        must stay above the restore floor: below it a restored engine holds
+        zeros where an uninterrupted one holds data."""
+        end = self.nproc + self._dstate_gather_extra
+        if max(end - reach, 0) < self._proc_floor:
+            raise ValueError(
+                f"window reaches back to grid point {max(end - reach, 0)} "
+                f"but this engine was restored with processed points from "
+                f"{self._proc_floor} on only (snapshot with a larger keep)")
+
+    def _snap_buffers(self, numel: int):
+        """The reused device staging and pinned host buffers, grown to hold
+        ``numel`` floats."""
+        if self._snap_dev is None or self._snap_dev.numel() < numel:
+            cap = numel + numel // 4
+            self._snap_dev = torch.empty(cap, device=self.device)
+            self._snap_host = torch.empty(cap, pin_memory=True)
+        return self._snap_dev[:numel], self._snap_host[:numel]
+
+    def snapshot(self, sids=None, keep: Optional[int] = None
+                 ) -> EngineSnapshot:
+        """The live tail of the listed streams' rings (all S streams when
+        ``sids`` is None) with the ring indices and geometry: per stream and
+        channel the ``nbk`` = max(head, cleared) - nproc (sum, cnt) bucket
+        pairs from ``nproc`` on, the last ``keep`` processed points and the
+        fill carry, each ring range unwrapped to linear grid order. That is
+        all ``restore`` needs to continue on a fresh engine exactly as this
+        one would.
+
+        ``keep`` defaults to ``model_win`` (or the points produced so far,
+        if fewer): enough for ``windows(batch=1)``. Raise it, up to
+        ``G - win_buckets`` (one model window is always allowed), when the
+        restored engine must serve batched windows reaching further back.
+
+        GPU: one launch into a reused device buffer and one copy into a
+        reused pinned host buffer; the returned ``payload`` is a view of
+        that host buffer, valid until this engine's next ``snapshot``.
+        Duplicate ids are harmless. Reads host ring positions only (legal
+        between graph replays)."""
+        assert self._dstate is None, "not inside a device_state block"
+        ids = np.arange(self.S, dtype=np.int64) if sids is None \
+            else self._check_sids(sids)
+        have = self.nproc - self._proc_floor
+        if keep is None:
+            keep = min(self.model_win, have,
+                       max(0, self.nproc - self._origin_nproc))
+        keep = int(keep)
+        # one model window always fits (windows() needs model_win <= G)
+        cap = min(max(self.G - self.win_buckets, min(self.model_win, self.G)),
+                  have)
+        if not 0 <= keep <= cap:
+            raise ValueError(
+                f"keep={keep} outside [0, {cap}]: G - win_buckets (or one "
+                f"model window) at the most, and this engine holds {have} "
+                f"processed points")
+        nbk = max(self.head, self._cleared) - self.nproc
+        assert 0 <= nbk <= self.G, (self.head, self._cleared, self.nproc)
+        n, R = int(ids.size), 2 * nbk + keep + 1
+        if n == 0:
+            payload = np.empty((0, self.C, R), dtype=np.float32)
+        elif self._gpu:
+            dids = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+            dev, host = self._snap_buffers(n * self.C * R)
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_snapshot_streams(
+                hip.ptr(dids), n, hip.ptr(self.bsum), hip.ptr(self.bcnt),
+                hip.ptr(self.proc), hip.ptr(self.last_val), self.S, self.C,
+                self.G, self._bst, self.nproc, nbk, keep, hip.ptr(dev),
+                hip.stream_ptr()), "tskd_preproc_snapshot_streams")
+            host.copy_(dev, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            payload = host.numpy().reshape(n, self.C, R)
+        else:
+            payload = np.empty((n, self.C, R), dtype=np.float32)
+            ch = np.arange(self.C)
+            bidx = (self.nproc + np.arange(nbk)) % self.G
+            pidx = (self.nproc - keep + np.arange(keep)) % self.G
+            payload[:, :, 0:2 * nbk:2] = \
+                self.bsum.numpy()[np.ix_(ids, ch, bidx)]
+            payload[:, :, 1:2 * nbk:2] = \
+                self.bcnt.numpy()[np.ix_(ids, ch, bidx)]
+            payload[:, :, 2 * nbk:2 * nbk + keep] = \
+                self.proc.numpy()[np.ix_(ids, ch, pidx)]
+            payload[:, :, -1] = self.last_val.numpy()[ids]
+        return EngineSnapshot(
+            geometry=self._geometry(), head=self.head, nproc=self.nproc,
+            cleared=self._cleared, origin_nproc=self._origin_nproc,
+            forced_ready=self._forced_ready, nbk=nbk, keep=keep, sids=ids,
+            born=self.born[ids].copy(), payload=payload)
+
+    def restore(self, snap: EngineSnapshot, sid_map=None) -> None:
+        """Continue where ``snap`` was taken: scatter its records into the
+        rings and take over its ring indices and ``born``. Only on a fresh
+        engine (nothing ingested yet) of the same geometry; ring length,
+        stream count and bucket packing may differ from the source's.
+        ``sid_map``: {source stream id: target slot} for every snapshot
+        stream (default: the same ids). Every check runs before anything is written, so a
+        ValueError leaves the engine fresh. Processed points older than
+        ``nproc - keep`` are not carried over: ``windows`` refuses to reach
+        below that floor."""
+        if self.head or self.nproc or self._cleared:
+            raise ValueError("restore needs a fresh engine "
+                             f"(head={self.head}, nproc={self.nproc})")
+        mine = self._geometry()
+        for k in GEOMETRY:
+            if snap.geometry.get(k) != mine[k]:
+                raise ValueError(f"geometry mismatch: {k} is "
+                                 f"{snap.geometry.get(k)} in the snapshot, "
+                                 f"{mine[k]} here")
+        nbk, keep, nproc = int(snap.nbk), int(snap.keep), int(snap.nproc)
+        if not (0 <= keep <= nproc and nbk >= 0
+                and nbk == max(snap.head, snap.cleared) - nproc):
+            raise ValueError("inconsistent snapshot indices")
+        if keep > self.G or nbk > self.G:
+            raise ValueError(
+                f"snapshot tail (nbk={nbk}, keep={keep}) does not fit a ring "
+                f"of G={self.G}")
+        src = np.asarray(snap.sids, dtype=np.int64).reshape(-1)
+        if sid_map is None:
+            dst = src
+        else:
+            try:
+                dst = np.asarray([sid_map[int(s)] for s in src])
+            except KeyError as e:
+                raise ValueError(f"sid_map lacks source stream {e}") from e
+        n, R = int(src.size), 2 * nbk + keep + 1
+        payload = np.asarray(snap.payload)
+        if payload.shape != (n, self.C, R) \
+                or payload.dtype != np.float32 or len(snap.born) != n:
+            raise ValueError("snapshot arrays do not match its stream list")
+        dst = self._check_sids(dst)
+        if np.unique(dst).size != n:
+            raise ValueError("duplicate target stream ids")
+        if n and self._gpu:
+            dids = torch.from_numpy(dst.astype(np.int32)).to(self.device)
+            rec = torch.from_numpy(np.ascontiguousarray(payload)) \
+                .to(self.device)
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_restore_streams(
+                hip.ptr(dids), n, hip.ptr(self.bsum), hip.ptr(self.bcnt),
+                hip.ptr(self.proc), hip.ptr(self.last_val), self.S, self.C,
+                self.G, self._bst, nproc, nbk, keep, hip.ptr(rec),
+                hip.stream_ptr()), "tskd_preproc_restore_streams")
+        elif n:
+            ch = np.arange(self.C)
+            bidx = (nproc + np.arange(nbk)) % self.G
+            pidx = (nproc - keep + np.arange(keep)) % self.G
+            self.bsum.numpy()[np.ix_(dst, ch, bidx)] = \
+                payload[:, :, 0:2 * nbk:2]
+            self.bcnt.numpy()[np.ix_(dst, ch, bidx)] = \
+                payload[:, :, 1:2 * nbk:2]
+            self.proc.numpy()[np.ix_(dst, ch, pidx)] = \
+                payload[:, :, 2 * nbk:2 * nbk + keep]
+            self.last_val.numpy()[dst] = payload[:, :, -1]
+        self.head, self.nproc = int(snap.head), nproc
+        self._cleared = int(snap.cleared)
+        self._origin_nproc = int(snap.origin_nproc)
+        self._forced_ready = self._forced_ready or bool(snap.forced_ready)
+        self.born[dst] = np.asarray(snap.born, dtype=np.int64)
+        self._proc_floor = nproc - keep
 
 
 class TriggerGraph:

@@ -16,7 +16,9 @@ from typing import Dict, Optional
 
 
 STREAM_STATES = ("active", "admitted_total", "evicted_total",
-                 "rejected_total")
+                 "rejected_total",
+                 # warm restart: state files refused at start (cold starts)
+                 "restore_failed")
 
 
 class StageTimer:

@@ -298,6 +298,58 @@ __global__ __launch_bounds__(256) void reset_streams_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// 1d. Stream snapshot / restore (warm restart): only a short tail of each
+//     ring is live — buckets [nproc, nproc+nbk) not yet consumed by the fill,
+//     the last `keep` processed points [nproc-keep, nproc) that model windows
+//     still read, and the fill carry. snapshot_streams compacts that tail of
+//     the listed streams into one record each; restore_streams scatters
+//     records back into a (fresh) engine whose G, S or bucket packing may
+//     differ from the source's.
+// ---------------------------------------------------------------------------
+// Record of stream k, C x R fp32 with R = 2*nbk + keep + 1, per channel:
+//   [sum0, cnt0, sum1, cnt1, ...](nbk pairs) [proc](keep) [last_val]
+// in LINEAR grid order: ring slot = start + j, minus G once past the end
+// (b0, p0 < G and nbk, keep <= G, so a range wraps at most once). The pair
+// layout is the same for BST=2 (packed) and BST=1 (split) engines. Lane u of
+// a record walks one channel's ring row with consecutive lanes on consecutive
+// addresses. blockIdx.y strides the id list, blockIdx.x the record. Ring
+// positions arrive by value (no device state block is read), so both kernels
+// may run between graph replays. Offsets into rings and records are 64-bit.
+template <bool RESTORE>
+__global__ __launch_bounds__(256) void snapshot_streams_kernel(
+    const int* __restrict__ sids, int n, float* bsum, float* bcnt,
+    float* proc, float* last_val, int S, int C, int G, int BST,
+    int b0, int p0, int nbk, int keep, float* rec_base)
+{
+    const int R = 2 * nbk + keep + 1;
+    const long total = (long)C * R;  // < 2^31 (the launcher's bound)
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const int s = sids[k];
+        if ((unsigned)s >= (unsigned)S) continue;  // host range-checks too
+        float* rec = rec_base + (long)k * total;
+        for (long u = (long)blockIdx.x * blockDim.x + threadIdx.x; u < total;
+             u += (long)gridDim.x * blockDim.x) {
+            const int c = (int)(u / R), r = (int)(u - (long)c * R);
+            const long row = (long)s * C + c;
+            float* p;
+            if (r < 2 * nbk) {
+                int g = b0 + (r >> 1);
+                if (g >= G) g -= G;
+                p = ((r & 1) ? bcnt : bsum) + (row * G + g) * BST;
+            } else if (r < 2 * nbk + keep) {
+                int g = p0 + (r - 2 * nbk);
+                if (g >= G) g -= G;
+                p = proc + row * G + g;
+            } else {
+                p = last_val + row;
+            }
+            if (RESTORE) *p = rec[u];
+            else rec[u] = *p;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // 2. Sliding-window average + ffill/bfill/zero-fill
 //    Processes proc grid points [phead, phead+np): window starting at grid j
 //    averages buckets [j, j+win_buckets). One thread per (s, c): the fill is
@@ -756,6 +808,57 @@ int tskd_preproc_reset_streams(const int* sids, int n, float* bsum,
     hipLaunchKernelGGL(reset_streams_kernel, dim3(gx, gy), dim3(256), 0,
                        (hipStream_t)stream, sids, n, rg, last_val, S, C);
     return (int)hipGetLastError();
+}
+
+// Shared launcher of snapshot_streams / restore_streams. -4: a shape or range
+// the kernels do not cover; -5: bst=2 without (sum,cnt) pairs.
+static int launch_snapshot(bool restore, const int* sids, int n, float* bsum,
+                           float* bcnt, float* proc, float* last_val, int S,
+                           int C, int G, int bst, long nproc, int nbk,
+                           int keep, float* rec, hipStream_t st) {
+    if (n <= 0) return 0;
+    if (S <= 0 || C <= 0 || G <= 0 || nproc < 0) return -4;
+    if (nbk < 0 || keep < 0 || nbk > G || keep > G || keep > nproc) return -4;
+    if (bst != 1 && bst != 2) return -5;
+    if (bst == 2 && bcnt != bsum + 1) return -5;
+    const long total = (long)C * (2L * nbk + keep + 1);
+    if (total > 0x7fffffffL) return -4;
+    const int b0 = (int)(nproc % G), p0 = (int)((nproc - keep) % G);
+    // ~8192 blocks over (ids x record chunks), as reset_streams sizes its grid
+    const int gy = n < 8192 ? n : 8192;
+    long gx = (total + 255) / 256;
+    if (gx > 8192 / gy) gx = 8192 / gy;
+    if (gx < 1) gx = 1;
+    if (restore)
+        hipLaunchKernelGGL((snapshot_streams_kernel<true>), dim3((int)gx, gy),
+                           dim3(256), 0, st, sids, n, bsum, bcnt, proc,
+                           last_val, S, C, G, bst, b0, p0, nbk, keep, rec);
+    else
+        hipLaunchKernelGGL((snapshot_streams_kernel<false>),
+                           dim3((int)gx, gy), dim3(256), 0, st, sids, n, bsum,
+                           bcnt, proc, last_val, S, C, G, bst, b0, p0, nbk,
+                           keep, rec);
+    return (int)hipGetLastError();
+}
+
+int tskd_preproc_snapshot_streams(const int* sids, int n, const float* bsum,
+                                  const float* bcnt, const float* proc,
+                                  const float* last_val, int S, int C, int G,
+                                  int bst, long nproc, int nbk, int keep,
+                                  float* out, void* stream) {
+    return launch_snapshot(false, sids, n, (float*)bsum, (float*)bcnt,
+                           (float*)proc, (float*)last_val, S, C, G, bst,
+                           nproc, nbk, keep, out, (hipStream_t)stream);
+}
+
+int tskd_preproc_restore_streams(const int* sids, int n, float* bsum,
+                                 float* bcnt, float* proc, float* last_val,
+                                 int S, int C, int G, int bst, long nproc,
+                                 int nbk, int keep, const float* in,
+                                 void* stream) {
+    return launch_snapshot(true, sids, n, bsum, bcnt, proc, last_val, S, C, G,
+                           bst, nproc, nbk, keep, (float*)in,
+                           (hipStream_t)stream);
 }
 
 int tskd_preproc_window_fill(const float* bsum, const float* bcnt, float* proc,

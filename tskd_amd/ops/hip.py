@@ -37,6 +37,10 @@ SIGNATURES = {
         "tskd_preproc_ingest_events": [P, P, P, P, P, P, I, I, L, L, I, P],
         "tskd_preproc_clear_buckets": [P, P, I, I, I, L, I, I, P],
         "tskd_preproc_reset_streams": [P, I, P, P, P, P, I, I, I, I, P],
+        "tskd_preproc_snapshot_streams": [P, I, P, P, P, P, I, I, I, I, L, I,
+                                          I, P, P],
+        "tskd_preproc_restore_streams": [P, I, P, P, P, P, I, I, I, I, L, I,
+                                         I, P, P],
         "tskd_preproc_window_fill": [P, P, P, P, I, I, I, L, I, I, P, I, P],
         "tskd_preproc_advance_state": [P, I, I, P],
         "tskd_preproc_window_gather": [P, P, I, I, I, I, I, I, I, I, L, P, I,

@@ -85,6 +85,9 @@ STAGES = {
     "processstream": "tskd_amd.cli.processstream",
     "predictstream": "tskd_amd.cli.predictstream",
     "plotdata": "tskd_amd.cli.plotdata",
+    # the fused daemon: run it with `-- --state-dir DIR` and a respawned
+    # process resumes rings, slot ids and offsets from its state file
+    "serve": "tskd_amd.cli.serve",
 }
 
 
