@@ -604,6 +604,143 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
     }
 }
 
+// Staged steady-state fill (packed layout, the default): the loop above has
+// every lane fetch its own 36 pairs from L1 — 48 lanes x 288 B requested for
+// ~1.5 KB of distinct data per wave, in nine dependent round trips. Here each
+// 16-lane group loads its row's span (np + win_buckets - 1 pairs, 47 in
+// steady state) ONCE, all of a lane's loads issued back to back, into a
+// per-group LDS row; slot j holds ring element (phead + j) mod G. Every lane
+// then sums its window from LDS with the loop above's exact association:
+// segment 1 (up to the ring end) dealt round-robin into a0..a3 with the < 4
+// remainder into a0, segment 2 again from a0, then (a0 + a1) + (a2 + a3).
+// When no lane of the launch wraps (uniform) and win_buckets is the
+// compile-time WB, the sum is WB unrolled LDS reads and packed adds. A wave's
+// next task's loads are issued before the current task's sums, so they are
+// in flight across its scan and store.
+// Row stride 80 pairs = 160 dwords = 32 mod 64 banks: the two groups of a
+// 32-lane ds_read_b64 half hit disjoint banks.
+#define F16_SLOTS 64    // pair slots a group's LDS row holds (span limit)
+#define F16_STRIDE 80   // row stride, pairs
+// NQ = loads per lane = ceil(span / 16), a launch constant so the loads and
+// the LDS stores are straight-line code.
+template <int WB, int NQ>
+__global__ __launch_bounds__(256) void window_fill16_staged_kernel(
+    const float* __restrict__ bsum, float* __restrict__ proc,
+    float* __restrict__ last_val, int S, int C, int G, long phead_in, int np,
+    int win_buckets, const long long* __restrict__ dstate)
+{
+    static_assert(WB % 4 == 0 && WB + 15 <= F16_SLOTS, "");
+    static_assert(NQ >= 1 && NQ * 16 <= F16_SLOTS, "");
+    const long phead = ring_nproc(dstate, phead_in);
+    const int wb = WB ? WB : win_buckets;
+    __shared__ f32x2p_ lds_p[4][4][F16_STRIDE];
+    __shared__ float lds_v[4][64];        // per wave: 4 groups x 16 values
+    const int wave = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    const int grp = lane / 16, gl = lane % 16;
+    float* lv = lds_v[wave] + grp * 16;
+    f32x2p_* row = lds_p[wave][grp];
+
+    const int s0 = (int)(phead % G);
+    const int span = np + wb - 1;         // <= 16 NQ, <= G (launcher)
+    const bool nowrap = s0 + span <= G;   // uniform over the grid
+    // ring element of slot gl + 16 q, unwrapped once (span <= G)
+    int eidx[NQ];
+    #pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        int e = s0 + gl + 16 * q;
+        if (e >= G) e -= G;
+        eidx[q] = gl + 16 * q < span ? e : 0;
+    }
+
+    const long nsc = (long)S * C;
+    const long stride = (long)gridDim.x * 16;
+    long sc0 = ((long)blockIdx.x * 4 + wave) * 4;
+    // a task's loads are issued one task ahead: they fly over the previous
+    // task's sums, scan and store
+    f32x2p_ ld[NQ];
+    float carry_ld = NAN;
+    auto fetch = [&](long base) {
+        const long sc = base + grp;
+        if (sc < nsc) {
+            const f32x2p_* pk = (const f32x2p_*)(bsum + sc * G * 2);
+            #pragma unroll
+            for (int q = 0; q < NQ; ++q) ld[q] = pk[eidx[q]];
+            carry_ld = last_val[sc];
+        }
+    };
+    if (sc0 < nsc) fetch(sc0);
+    for (; sc0 < nsc; sc0 += stride) {
+        const long sc = sc0 + grp;
+        const bool live = sc < nsc;
+        float carry = NAN, first_val = NAN, val = NAN;
+        int nan_prefix = 0;
+        if (live) {
+            carry = carry_ld;
+            #pragma unroll
+            for (int q = 0; q < NQ; ++q) row[gl + 16 * q] = ld[q];
+        }
+        if (sc0 + stride < nsc) fetch(sc0 + stride);
+        wave_sync();
+        if (live && gl < np) {
+            f32x2p_ a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+            f32x2p_ a2 = {0.f, 0.f}, a3 = {0.f, 0.f};
+            const f32x2p_* p1 = row + gl;
+            if (WB && nowrap) {
+                #pragma unroll
+                for (int k = 0; k < WB; k += 4) {
+                    a0 += p1[k];     a1 += p1[k + 1];
+                    a2 += p1[k + 2]; a3 += p1[k + 3];
+                }
+            } else {
+                const int start = (int)((phead + gl) % G);
+                const int first = min(wb, G - start);
+                const int rem = wb - first;
+                int k = 0;
+                for (; k + 4 <= first; k += 4) {
+                    a0 += p1[k];     a1 += p1[k + 1];
+                    a2 += p1[k + 2]; a3 += p1[k + 3];
+                }
+                for (; k < first; ++k) a0 += p1[k];
+                const f32x2p_* p2 = p1 + first;
+                int j = 0;
+                for (; j + 4 <= rem; j += 4) {
+                    a0 += p2[j];     a1 += p2[j + 1];
+                    a2 += p2[j + 2]; a3 += p2[j + 3];
+                }
+                for (; j < rem; ++j) a0 += p2[j];
+            }
+            const f32x2p_ t = (a0 + a1) + (a2 + a3);
+            val = (t.y > 0.f) ? t.x / t.y : NAN;
+        }
+        lv[gl] = val;
+        wave_sync();
+        if (live && gl == 0) {            // serial ffill scan per group
+            for (int j = 0; j < np; ++j) {
+                const float v = lv[j];
+                if (isnan(v)) {
+                    if (isnan(carry)) ++nan_prefix;   // before first value
+                    else lv[j] = carry;
+                } else {
+                    if (isnan(carry)) first_val = v;
+                    carry = v;
+                }
+            }
+            last_val[sc] = carry;
+        }
+        wave_sync();
+        if (live && gl < np) {
+            nan_prefix = __shfl(nan_prefix, grp * 16);
+            first_val = __shfl(first_val, grp * 16);
+            float outv = lv[gl];
+            if (gl < nan_prefix)          // bfill | fillna(0) prefix
+                outv = isnan(first_val) ? 0.f : first_val;
+            proc[sc * G + (phead + gl) % G] = outv;
+        }
+        wave_sync();                      // row and lv reads done before reuse
+    }
+}
+
 // ---------------------------------------------------------------------------
 // 3. Window gather: (S, B, C, WIN) model inputs from processed grid.
 //    Window b (b = 0..B-1) covers grid [end - (B-1-b)*stride - WIN,
@@ -869,6 +1006,24 @@ int tskd_preproc_window_fill(const float* bsum, const float* bcnt, float* proc,
     if (np <= 16) {
         // steady-state: 4 (stream, channel) rows per wave, 16-lane groups
         const long nsc4 = ((long)S * C + 15) / 16;
+        // TSKD_FILL16_STAGED (default 1, read per launch so both live in one
+        // process): packed rows whose span fits the LDS row and the ring are
+        // staged once per group; 0 keeps the per-lane L1 loop below.
+        const char* sk = getenv("TSKD_FILL16_STAGED");
+        const int span = np + win_buckets - 1;
+        if (bst == 2 && win_buckets >= 1 && span <= F16_SLOTS && span <= G &&
+            !(sk && atoi(sk) == 0)) {
+            const dim3 grid(grid_for(nsc4, 1));
+#define FILL16_STAGED(WB, NQ)                                                 \
+    hipLaunchKernelGGL((window_fill16_staged_kernel<WB, NQ>), grid,           \
+                       dim3(256), 0, (hipStream_t)stream, bsum, proc,         \
+                       last_val, S, C, G, phead, np, win_buckets, dstate)
+            if (win_buckets == 36 && span <= 48) FILL16_STAGED(36, 3);
+            else if (win_buckets == 36) FILL16_STAGED(36, 4);
+            else FILL16_STAGED(0, 4);
+#undef FILL16_STAGED
+            return (int)hipGetLastError();
+        }
         hipLaunchKernelGGL(window_fill16_kernel, dim3(grid_for(nsc4, 1)),
                            dim3(256), 0, (hipStream_t)stream, bsum, bcnt,
                            proc, last_val, S, C, G, phead, np, win_buckets,
