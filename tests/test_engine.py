@@ -194,6 +194,16 @@ class TestStreamEngineCPU:
                                    atol=1e-5)
 
 
+def test_engine_window_bound_is_the_kernels():
+    """GPU_MAX_WIN_BUCKETS (stream_engine.py) == FILL_MAXW (the .hip file)."""
+    import re
+    from tskd_amd.engine import stream_engine
+    from tskd_amd.ops import build
+    with open(build.CSRC + "/preprocess_kernels.hip", encoding="utf-8") as fh:
+        maxw = re.search(r"^#define FILL_MAXW (\d+)$", fh.read(), re.M)
+    assert int(maxw.group(1)) == stream_engine.GPU_MAX_WIN_BUCKETS == 64
+
+
 @pytest.mark.gpu
 class TestStreamEngineGPU:
     def test_gpu_matches_cpu_dense(self):
@@ -214,6 +224,44 @@ class TestStreamEngineGPU:
         wg = gpu.windows(batch=3, stride=12)
         np.testing.assert_allclose(wg.cpu().numpy(), wc.numpy(), rtol=1e-4,
                                    atol=1e-5)
+
+    def test_window_length_bound(self):
+        """The fill kernels take 1 <= win_buckets <= 64 (the general
+        kernel's LDS rows are sized for that): a longer window is refused
+        by the engine and by the launcher, which launches nothing; 64 itself
+        works through the general kernel (np = 20) and the per-lane fill16
+        kernel (np = 12: the span of 75 pairs exceeds the staged row)."""
+        S, C, G, fs = 1, 2, 256, 25.0
+        with pytest.raises(ValueError):
+            StreamEngine(S, C, ring_grid=G, win_buckets=65, device="cuda")
+        gpu = StreamEngine(S, C, ring_grid=G, fs=fs, win_buckets=64,
+                           device="cuda")
+        gpu.proc.fill_(7.25)
+        # past the constructor's check, through the engine's own binding of
+        # tskd_preproc_window_fill: hip.check reports the launcher's -4
+        for npn, win in ((20, 65), (12, 65), (12, 0)):
+            gpu.win_buckets = win
+            with pytest.raises(RuntimeError, match="window_fill failed: "
+                                                   "code -4$"):
+                gpu._launch_fill(0, npn)
+        torch.cuda.synchronize()
+        assert (gpu.proc == 7.25).all()    # nothing ran
+        gpu.win_buckets = 64
+        gpu.proc.zero_()
+        cpu = StreamEngine(S, C, ring_grid=G, fs=fs, win_buckets=64)
+        raw = _dense_raw(S, C, gpu.bucket_len * (83 + 12), seed=23,
+                         nan_frac=0.1)
+        for lo, hi, npn in ((0, 83, 20), (83, 95, 12)):
+            chunk = raw[:, :, lo * gpu.bucket_len:hi * gpu.bucket_len]
+            before = gpu.nproc
+            cpu.ingest_dense(chunk)
+            gpu.ingest_dense(chunk.cuda())
+            torch.cuda.synchronize()
+            assert gpu.nproc - before == npn and gpu.nproc == cpu.nproc
+            np.testing.assert_allclose(
+                gpu.proc[:, :, :gpu.nproc].cpu().numpy(),
+                cpu.proc[:, :, :cpu.nproc].numpy(), rtol=1e-4, atol=1e-5)
+        assert cpu.proc[:, :, :32].abs().min() > 0    # every point filled
 
     def test_gpu_bf16_dense_with_nans_matches_cpu(self):
         """bf16 dense ingest takes the masked-boundary kernel (mode 5) —

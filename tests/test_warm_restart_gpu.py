@@ -12,9 +12,10 @@ import torch
 from tskd_amd.engine import StreamEngine
 
 from test_stream_lifecycle_gpu import _filled_engine
-from test_warm_restart import (C, G, POINTS, S, check_cold_starts,
-                               check_daemon, check_isolation, check_refusals,
-                               check_resumed, reference_run, run_daemon)
+from test_warm_restart import (C, G, POINTS, S, _filled_cpu,
+                               check_cold_starts, check_daemon,
+                               check_isolation, check_refusals, check_resumed,
+                               reference_run, run_daemon)
 
 pytestmark = pytest.mark.gpu
 
@@ -75,6 +76,16 @@ class TestSnapshotKernels:
         snap = check_isolation(src, fresh)
         if src_packed == dst_packed:
             check_refusals(snap, fresh)
+
+    @pytest.mark.parametrize("src,dst", [("cpu", "cuda"), ("cuda", "cpu")])
+    def test_records_cross_between_cpu_and_cuda(self, src, dst, monkeypatch):
+        """A snapshot taken by one implementation (numpy gather or kernel)
+        restored by the other: check_isolation compares both payloads with
+        the same numpy gather of the source's views, bit for bit."""
+        filled = _filled_cpu() if src == "cpu" \
+            else _filled_engine(S, C, G, True, monkeypatch)
+        check_isolation(filled,
+                        lambda: StreamEngine(S, C, ring_grid=G, device=dst))
 
     def test_snapshot_reuses_its_buffers(self, monkeypatch):
         e = _filled_engine(S, C, G, True, monkeypatch)

@@ -29,6 +29,10 @@ from tskd_amd.engine import windowing as W
 from tskd_amd.engine.snapshot import GEOMETRY, EngineSnapshot
 from tskd_amd.ops import hip
 
+# longest window the GPU fill kernels take: FILL_MAXW in
+# preprocess_kernels.hip (tests/test_engine.py holds the two together)
+GPU_MAX_WIN_BUCKETS = 64
+
 
 class StreamEngine:
     """Event-time sliding-window engine over S streams x C channels.
@@ -62,6 +66,10 @@ class StreamEngine:
         # window_fill reads each bucket with ONE f32x2 load. bsum/bcnt stay
         # the public (S, C, G) views; kernels take the element stride.
         self._gpu = dev.type == "cuda"
+        if self._gpu and not 1 <= win_buckets <= GPU_MAX_WIN_BUCKETS:
+            raise ValueError(
+                f"win_buckets={win_buckets} outside [1, "
+                f"{GPU_MAX_WIN_BUCKETS}]: the fill kernels' window limit")
         self._packed = self._gpu and \
             os.environ.get("TSKD_PACKED_BUCKETS", "1") != "0"
         if self._packed:

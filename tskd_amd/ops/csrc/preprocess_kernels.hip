@@ -352,14 +352,98 @@ __global__ __launch_bounds__(256) void snapshot_streams_kernel(
 // ---------------------------------------------------------------------------
 // 2. Sliding-window average + ffill/bfill/zero-fill
 //    Processes proc grid points [phead, phead+np): window starting at grid j
-//    averages buckets [j, j+win_buckets). One thread per (s, c): the fill is
-//    an order-dependent scan (tiny np per trigger; np can be large in replay
-//    catch-up, still coalesced across the S*C threads).
+//    averages buckets [j, j+win_buckets). The fill is an order-dependent
+//    scan per (s, c) row: tiny np per trigger, large only in replay catch-up.
+//    Three kernels (general, fill16, staged fill16) share the pieces below.
 // ---------------------------------------------------------------------------
-// One WAVE per (stream, channel): coalesced bucket loads, LDS-staged sliding
-// sums (each lane owns one output point per 64-point chunk), the
-// order-dependent ffill scan runs on lane 0 over LDS (np is small per
-// trigger; large only in replay catch-up, still chunked).
+// Longest window any fill kernel accepts (the launcher refuses others): it
+// sizes the general kernel's LDS rows.
+#define FILL_MAXW 64
+
+// Serial ffill scan of window values lv[0, n), in place, by ONE lane. After
+// ffill-with-carry, NaNs can only be a PREFIX of the batch (once any value
+// is seen, carry is set forever), so bfill reduces to: fill the prefix with
+// the first valid value (or 0). nan_prefix accumulates over calls (the
+// general kernel scans one 64-point chunk per call); first_val is the value
+// that ended the prefix.
+__device__ __forceinline__ void fill_scan(float* lv, int n, float& carry,
+                                          int& nan_prefix, float& first_val) {
+    for (int j = 0; j < n; ++j) {
+        const float v = lv[j];
+        if (isnan(v)) {
+            if (isnan(carry)) ++nan_prefix;  // still before the first value
+            else lv[j] = carry;
+        } else {
+            if (isnan(carry)) first_val = v;
+            carry = v;
+        }
+    }
+}
+
+// Window (sum, cnt) over two linear segments of pairs — a window that wraps
+// the ring is p1[0, first) then p2[0, rem). Four independent accumulators (a
+// single dependent add chain was the lane's critical path) in a fixed
+// association that every caller shares bit for bit: segment 1 dealt
+// round-robin into a0..a3 with the < 4 remainder into a0, segment 2 again
+// from a0, then (a0 + a1) + (a2 + a3).
+__device__ __forceinline__ f32x2p_ window_sum2(const f32x2p_* p1, int first,
+                                               const f32x2p_* p2, int rem) {
+    f32x2p_ a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+    f32x2p_ a2 = {0.f, 0.f}, a3 = {0.f, 0.f};
+    int k = 0;
+    for (; k + 4 <= first; k += 4) {
+        a0 += p1[k];     a1 += p1[k + 1];
+        a2 += p1[k + 2]; a3 += p1[k + 3];
+    }
+    for (; k < first; ++k) a0 += p1[k];
+    int j = 0;
+    for (; j + 4 <= rem; j += 4) {
+        a0 += p2[j];     a1 += p2[j + 1];
+        a2 += p2[j + 2]; a3 += p2[j + 3];
+    }
+    for (; j < rem; ++j) a0 += p2[j];
+    return (a0 + a1) + (a2 + a3);
+}
+
+// Window value of a (sum, cnt) total: the mean, NaN for an empty window.
+__device__ __forceinline__ float window_mean(f32x2p_ t) {
+    return (t.y > 0.f) ? t.x / t.y : NAN;
+}
+
+// fill16 epilogue: lane gl of a 16-lane group holds window value `val` of
+// row sc (NaN = empty window); lv is the group's 16-float LDS row. Lane 0 of
+// the group scans, the group takes the bfill | fillna(0) prefix from it and
+// stores its np points at proc[sc, (phead + gl) mod G]; the row's carry goes
+// back to last_val. Whole waves call it (it syncs the wave three times).
+__device__ __forceinline__ void fill16_finish(
+    float* lv, float val, float carry, bool live, long sc, int grp, int gl,
+    int np, long phead, int G, float* __restrict__ proc,
+    float* __restrict__ last_val)
+{
+    float first_val = NAN;
+    int nan_prefix = 0;
+    lv[gl] = val;
+    wave_sync();
+    if (live && gl == 0) {
+        fill_scan(lv, np, carry, nan_prefix, first_val);
+        last_val[sc] = carry;
+    }
+    wave_sync();
+    if (live && gl < np) {
+        nan_prefix = __shfl(nan_prefix, grp * 16);
+        first_val = __shfl(first_val, grp * 16);
+        float outv = lv[gl];
+        if (gl < nan_prefix)
+            outv = isnan(first_val) ? 0.f : first_val;
+        proc[sc * G + (phead + gl) % G] = outv;
+    }
+    wave_sync();                          // lv reads done before reuse
+}
+
+// General kernel (np > 16: catch-up refills). One WAVE per (stream,
+// channel): coalesced bucket loads, LDS-staged sliding sums (each lane owns
+// one output point per 64-point chunk), the order-dependent ffill scan runs
+// on lane 0 over LDS.
 __global__ __launch_bounds__(256) void window_fill_kernel(
     const float* __restrict__ bsum, const float* __restrict__ bcnt,
     float* __restrict__ proc, float* __restrict__ last_val,
@@ -368,16 +452,15 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
 {
     const long phead = ring_nproc(dstate, phead_in);
     constexpr int CHUNK = 64;             // output points per iteration
-    const int MAXW = 64;                  // win_buckets <= 64 (default 36)
-    __shared__ float lds_s[4][CHUNK + 64];  // bucket sums (CHUNK+MAXW-1 used)
-    __shared__ float lds_c[4][CHUNK + 64];
+    // bucket sums / counts: CHUNK + win_buckets - 1 <= CHUNK + FILL_MAXW used
+    __shared__ float lds_s[4][CHUNK + FILL_MAXW];
+    __shared__ float lds_c[4][CHUNK + FILL_MAXW];
     __shared__ float lds_v[4][CHUNK];       // window values / filled output
     const int wave = threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
     float* ls = lds_s[wave];
     float* lc = lds_c[wave];
     float* lv = lds_v[wave];
-    (void)MAXW;
 
     const long nsc = (long)S * C;
     for (long sc = (long)blockIdx.x * 4 + wave; sc < nsc;
@@ -386,9 +469,6 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
         const float* bc = bcnt + sc * G * BST;
         float* pr = proc + sc * G;
         float carry = last_val[sc];
-        // After ffill-with-carry, NaNs can only be a PREFIX of the batch
-        // (once any value is seen, carry is set forever). bfill therefore
-        // reduces to: fill the prefix with the first valid value (or 0).
         int nan_prefix = 0;
         float first_val = NAN;
 
@@ -419,18 +499,7 @@ __global__ __launch_bounds__(256) void window_fill_kernel(
             }
             wave_sync();
             // lane 0: ffill scan (order-dependent; jn <= 64 steps)
-            if (lane == 0) {
-                for (int j = 0; j < jn; ++j) {
-                    const float v = lv[j];
-                    if (isnan(v)) {
-                        if (isnan(carry)) ++nan_prefix;  // still before 1st value
-                        else lv[j] = carry;
-                    } else {
-                        if (isnan(carry)) first_val = v;
-                        carry = v;
-                    }
-                }
-            }
+            if (lane == 0) fill_scan(lv, jn, carry, nan_prefix, first_val);
             wave_sync();
             if (lane < jn) pr[(phead + j0 + lane) % G] = lv[lane];
             wave_sync();
@@ -512,8 +581,7 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
          sc0 += (long)gridDim.x * 16) {
         const long sc = sc0 + grp;
         const bool live = sc < nsc;
-        float carry = NAN, first_val = NAN, val = NAN;
-        int nan_prefix = 0;
+        float carry = NAN, val = NAN;
         if (live) {
             carry = last_val[sc];
             if (gl < np && BST == 2) {
@@ -523,24 +591,8 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
                 const f32x2p_* pk = (const f32x2p_*)(bsum + sc * G * 2);
                 const int start = (int)((phead + gl) % G);
                 const int first = min(win_buckets, G - start);
-                const int rem = win_buckets - first;
-                f32x2p_ a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
-                f32x2p_ a2 = {0.f, 0.f}, a3 = {0.f, 0.f};
-                const f32x2p_* p1 = pk + start;
-                int k = 0;
-                for (; k + 4 <= first; k += 4) {
-                    a0 += p1[k];     a1 += p1[k + 1];
-                    a2 += p1[k + 2]; a3 += p1[k + 3];
-                }
-                for (; k < first; ++k) a0 += p1[k];
-                int j = 0;
-                for (; j + 4 <= rem; j += 4) {
-                    a0 += pk[j];     a1 += pk[j + 1];
-                    a2 += pk[j + 2]; a3 += pk[j + 3];
-                }
-                for (; j < rem; ++j) a0 += pk[j];
-                const f32x2p_ t = (a0 + a1) + (a2 + a3);
-                val = (t.y > 0.f) ? t.x / t.y : NAN;
+                val = window_mean(window_sum2(pk + start, first, pk,
+                                              win_buckets - first));
             } else if (gl < np) {
                 const float* bs = bsum + sc * G;
                 const float* bc = bcnt + sc * G;
@@ -576,31 +628,8 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
                 val = (cnt > 0.f) ? sum / cnt : NAN;
             }
         }
-        lv[gl] = val;
-        wave_sync();
-        if (live && gl == 0) {            // serial ffill scan per group
-            for (int j = 0; j < np; ++j) {
-                const float v = lv[j];
-                if (isnan(v)) {
-                    if (isnan(carry)) ++nan_prefix;   // before first value
-                    else lv[j] = carry;
-                } else {
-                    if (isnan(carry)) first_val = v;
-                    carry = v;
-                }
-            }
-            last_val[sc] = carry;
-        }
-        wave_sync();
-        if (live && gl < np) {
-            nan_prefix = __shfl(nan_prefix, grp * 16);
-            first_val = __shfl(first_val, grp * 16);
-            float outv = lv[gl];
-            if (gl < nan_prefix)          // bfill | fillna(0) prefix
-                outv = isnan(first_val) ? 0.f : first_val;
-            proc[sc * G + (phead + gl) % G] = outv;
-        }
-        wave_sync();
+        fill16_finish(lv, val, carry, live, sc, grp, gl, np, phead, G, proc,
+                      last_val);
     }
 }
 
@@ -610,9 +639,8 @@ __global__ __launch_bounds__(256) void window_fill16_kernel(
 // 16-lane group loads its row's span (np + win_buckets - 1 pairs, 47 in
 // steady state) ONCE, all of a lane's loads issued back to back, into a
 // per-group LDS row; slot j holds ring element (phead + j) mod G. Every lane
-// then sums its window from LDS with the loop above's exact association:
-// segment 1 (up to the ring end) dealt round-robin into a0..a3 with the < 4
-// remainder into a0, segment 2 again from a0, then (a0 + a1) + (a2 + a3).
+// then sums its window from LDS in window_sum2's association, so the two
+// kernels agree bit for bit.
 // When no lane of the launch wraps (uniform) and win_buckets is the
 // compile-time WB, the sum is WB unrolled LDS reads and packed adds. A wave's
 // next task's loads are issued before the current task's sums, so they are
@@ -673,8 +701,7 @@ __global__ __launch_bounds__(256) void window_fill16_staged_kernel(
     for (; sc0 < nsc; sc0 += stride) {
         const long sc = sc0 + grp;
         const bool live = sc < nsc;
-        float carry = NAN, first_val = NAN, val = NAN;
-        int nan_prefix = 0;
+        float carry = NAN, val = NAN;
         if (live) {
             carry = carry_ld;
             #pragma unroll
@@ -683,61 +710,27 @@ __global__ __launch_bounds__(256) void window_fill16_staged_kernel(
         if (sc0 + stride < nsc) fetch(sc0 + stride);
         wave_sync();
         if (live && gl < np) {
-            f32x2p_ a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
-            f32x2p_ a2 = {0.f, 0.f}, a3 = {0.f, 0.f};
             const f32x2p_* p1 = row + gl;
-            if (WB && nowrap) {
+            f32x2p_ t;
+            if (WB && nowrap) {           // window_sum2 with rem = 0, unrolled
+                f32x2p_ a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+                f32x2p_ a2 = {0.f, 0.f}, a3 = {0.f, 0.f};
                 #pragma unroll
                 for (int k = 0; k < WB; k += 4) {
                     a0 += p1[k];     a1 += p1[k + 1];
                     a2 += p1[k + 2]; a3 += p1[k + 3];
                 }
-            } else {
+                t = (a0 + a1) + (a2 + a3);
+            } else {                      // segment 2 follows in the LDS row
                 const int start = (int)((phead + gl) % G);
                 const int first = min(wb, G - start);
-                const int rem = wb - first;
-                int k = 0;
-                for (; k + 4 <= first; k += 4) {
-                    a0 += p1[k];     a1 += p1[k + 1];
-                    a2 += p1[k + 2]; a3 += p1[k + 3];
-                }
-                for (; k < first; ++k) a0 += p1[k];
-                const f32x2p_* p2 = p1 + first;
-                int j = 0;
-                for (; j + 4 <= rem; j += 4) {
-                    a0 += p2[j];     a1 += p2[j + 1];
-                    a2 += p2[j + 2]; a3 += p2[j + 3];
-                }
-                for (; j < rem; ++j) a0 += p2[j];
+                t = window_sum2(p1, first, p1 + first, wb - first);
             }
-            const f32x2p_ t = (a0 + a1) + (a2 + a3);
-            val = (t.y > 0.f) ? t.x / t.y : NAN;
+            val = window_mean(t);
         }
-        lv[gl] = val;
-        wave_sync();
-        if (live && gl == 0) {            // serial ffill scan per group
-            for (int j = 0; j < np; ++j) {
-                const float v = lv[j];
-                if (isnan(v)) {
-                    if (isnan(carry)) ++nan_prefix;   // before first value
-                    else lv[j] = carry;
-                } else {
-                    if (isnan(carry)) first_val = v;
-                    carry = v;
-                }
-            }
-            last_val[sc] = carry;
-        }
-        wave_sync();
-        if (live && gl < np) {
-            nan_prefix = __shfl(nan_prefix, grp * 16);
-            first_val = __shfl(first_val, grp * 16);
-            float outv = lv[gl];
-            if (gl < nan_prefix)          // bfill | fillna(0) prefix
-                outv = isnan(first_val) ? 0.f : first_val;
-            proc[sc * G + (phead + gl) % G] = outv;
-        }
-        wave_sync();                      // row and lv reads done before reuse
+        // its last sync: row and lv reads are done before the next task's
+        fill16_finish(lv, val, carry, live, sc, grp, gl, np, phead, G, proc,
+                      last_val);
     }
 }
 
@@ -1002,6 +995,8 @@ int tskd_preproc_window_fill(const float* bsum, const float* bcnt, float* proc,
                              float* last_val, int S, int C, int G, long phead,
                              int np, int win_buckets,
                              const long long* dstate, int bst, void* stream) {
+    // -4: a window the general kernel's LDS rows do not hold (every np)
+    if (win_buckets < 1 || win_buckets > FILL_MAXW) return -4;
     if (np <= 0) return 0;
     if (np <= 16) {
         // steady-state: 4 (stream, channel) rows per wave, 16-lane groups
@@ -1011,7 +1006,7 @@ int tskd_preproc_window_fill(const float* bsum, const float* bcnt, float* proc,
         // staged once per group; 0 keeps the per-lane L1 loop below.
         const char* sk = getenv("TSKD_FILL16_STAGED");
         const int span = np + win_buckets - 1;
-        if (bst == 2 && win_buckets >= 1 && span <= F16_SLOTS && span <= G &&
+        if (bst == 2 && span <= F16_SLOTS && span <= G &&
             !(sk && atoi(sk) == 0)) {
             const dim3 grid(grid_for(nsc4, 1));
 #define FILL16_STAGED(WB, NQ)                                                 \
