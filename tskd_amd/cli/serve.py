@@ -53,8 +53,17 @@ class FusedServer:
                  emit_processed: Optional[str] = None,
                  rank: int = 0, world: int = 1,
                  pipelined: bool = False, evict_idle_s: float = 0.0,
-                 state_path: Optional[str] = None, snapshot_every: int = 1):
+                 state_path: Optional[str] = None, snapshot_every: int = 1,
+                 min_coverage: float = 0.0):
         self.cfg = cfg
+        # coverage gate (opt-in; 0 = off): a stream whose latest model window
+        # holds less than this fraction of inputs that rest on samples (the
+        # rest being a carried, back-filled or zero value: se.coverage) is
+        # still scored, but its prediction goes neither to the store nor to
+        # the response topic
+        self.min_coverage = float(min_coverage)
+        if not 0.0 <= self.min_coverage <= 1.0:
+            raise ValueError(f"min_coverage={min_coverage} outside [0, 1]")
         # warm restart: every snapshot_every-th trigger ends by writing ONE
         # file (save_state) that a successor process resumes from
         # (load_state); None = off
@@ -402,25 +411,65 @@ class FusedServer:
             pad = torch.zeros(self.max_streams, device=probs.device)
             pad[:n_active] = probs
             self.last_gathered = all_gather_predictions(pad)
+        imputed = self._imputed_inputs(n_active) \
+            if self.min_coverage > 0.0 else None
         t0 = self._stamp("model", t0)
         if self.pipelined:
             # defer the device sync: persist at the next trigger start,
             # after the bus poll has overlapped this trigger's GPU work
-            self._pending = (probs, t_us, list(self.pids), mask)
+            self._pending = (probs, t_us, list(self.pids), mask, imputed)
         else:
-            self._persist(probs, t_us, self.pids, mask)
+            self._persist(probs, t_us, self.pids, mask, imputed)
         self._stamp("persist", t0)
         n_scored = n_active if mask is None else sum(mask)
         self.timer.add_items(n_scored)
         return n_scored
 
-    def _persist(self, probs, t_us: int, pids, mask=None) -> None:
+    def _imputed_inputs(self, n_active: int) -> Optional[torch.Tensor]:
+        """Per slot in use, the number of fabricated inputs of its latest
+        model window over the channels the config names (ring channels beyond
+        them are zero by construction): one coverage launch, left on the
+        device. None when the engine refuses (the window's buckets are no
+        longer wholly in the ring): that trigger withholds nothing."""
+        try:
+            cov = self.se.coverage()
+        except ValueError as e:
+            log.warning("coverage unavailable, nothing withheld: %s", e)
+            g = self.timer.gauges
+            g["coverage_unavailable"] = g.get("coverage_unavailable", 0) + 1
+            return None
+        return cov[:n_active, :self.cfg.n_channels, 1].sum(dim=1)
+
+    def _coverage_gate(self, imputed, n: int, mask):
+        """(q per slot, mask without the streams whose q < min_coverage);
+        counts the withheld ones."""
+        q = 1.0 - imputed.cpu().numpy()[:n].astype("float64") / (
+            self.se.model_win * self.cfg.n_channels)
+        base = [True] * n if mask is None else mask
+        held = [bool(b and q[i] < self.min_coverage)
+                for i, b in enumerate(base)]
+        g = self.timer.gauges
+        g["withheld_total"] = g.get("withheld_total", 0) + sum(held)
+        if any(base):
+            g["coverage_mean"] = float(
+                sum(q[i] for i, b in enumerate(base) if b) / sum(base))
+        return q, [b and not h for b, h in zip(base, held)]
+
+    def _persist(self, probs, t_us: int, pids, mask=None,
+                 imputed=None) -> None:
+        q = None
+        if imputed is not None:
+            q, mask = self._coverage_gate(imputed, len(pids), mask)
+            if not any(mask):
+                return
         if mask is not None:
             # lifecycle: only live, ready slots are persisted and published
             keep = [i for i, m in enumerate(mask) if m]
             probs = probs.reshape(-1)[:len(pids)][
                 torch.tensor(keep, dtype=torch.long, device=probs.device)]
             pids = [pids[i] for i in keep]
+            if q is not None:
+                q = q[keep]
         n = len(pids)
         if self.store is not None:
             # the mmap store is multi-process safe: each rank persists
@@ -431,17 +480,17 @@ class FusedServer:
         if self.producer and self.response_topic:
             vals = probs.reshape(-1)[:n].cpu()
             for i, pid in enumerate(pids):
+                cov = "" if q is None else f', "coverage": {q[i]:.4f}'
                 self.producer.produce(
                     self.response_topic, pid,
-                    f'{{"t_us": {t_us}, "risk": {float(vals[i]):.6f}}}')
+                    f'{{"t_us": {t_us}, "risk": {float(vals[i]):.6f}{cov}}}')
 
     def flush(self) -> None:
         """Persist the deferred trigger (pipelined mode; call on shutdown
         or whenever durability must catch up to compute)."""
         if self._pending is not None:
-            probs, t_us, pids, mask = self._pending
-            self._pending = None
-            self._persist(probs, t_us, pids, mask)
+            pending, self._pending = self._pending, None
+            self._persist(*pending)
 
     # ------------------------------------------------------------ warm restart
     def save_state(self, path: Optional[str] = None) -> None:
@@ -602,7 +651,14 @@ def main(argv=None) -> None:
     ap.add_argument("--snapshot-every", type=int, default=1, metavar="N",
                     help="with --state-dir: write the state file every N "
                          "triggers (and once more on SIGTERM)")
+    ap.add_argument("--min-coverage", type=float, default=0.0, metavar="F",
+                    help="coverage gate: withhold the prediction of a stream "
+                         "whose latest model window has less than this "
+                         "fraction of inputs resting on samples, the rest "
+                         "being carried, back-filled or zero (0 = off)")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.min_coverage <= 1.0:
+        ap.error("--min-coverage must lie in [0, 1]")
     if args.state_dir and args.poll_thread:
         ap.error("--state-dir cannot be combined with --poll-thread: the "
                  "poll thread owns the consumer, so the bus positions run "
@@ -628,7 +684,8 @@ def main(argv=None) -> None:
                       emit_processed=args.emit_processed,
                       rank=rank, world=world, pipelined=args.pipelined,
                       evict_idle_s=args.evict_idle_s,
-                      snapshot_every=args.snapshot_every)
+                      snapshot_every=args.snapshot_every,
+                      min_coverage=args.min_coverage)
     if args.state_dir:
         os.makedirs(args.state_dir, exist_ok=True)
         srv.state_path = state_file(args.state_dir, rank, world)

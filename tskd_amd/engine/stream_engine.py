@@ -94,6 +94,9 @@ class StreamEngine:
         # warm restart: processed points below this grid point were not
         # carried over by restore() (0 on an engine that was never restored)
         self._proc_floor = 0
+        # ... and buckets below this one neither: coverage() counts them as
+        # present (their state is unknown)
+        self._bucket_floor = 0
         self._snap_dev = self._snap_host = None  # reused staging buffers
         if self._gpu:
             hip.load(hip.PREPROC)  # fail here, not at the first launch
@@ -551,6 +554,79 @@ class StreamEngine:
         than 600 s are zero-padded, exactly as mid-history windows are)."""
         self._forced_ready = True
 
+    # ---------------------------------------------------------------- coverage
+    def coverage(self, sids=None) -> torch.Tensor:
+        """How much of the latest model window rests on samples: int32
+        ``(n, C, 3)`` = ``[present, imputed, stale]`` per listed stream (all
+        S when ``sids`` is None) and channel, on the engine's device.
+
+        The window's ``model_win`` grid points ``[lo, nproc)``, ``lo = nproc
+        - model_win``, average the ``span = model_win + win_buckets - 1``
+        buckets ``[lo, hi)``, ``hi = nproc + win_buckets - 1``. A bucket
+        ``b`` is present iff its count is > 0 or ``b`` lies below the restore
+        floor (the snapshot's ``nproc`` on a restored engine: buckets below
+        it were not carried over, and unknown counts as present).
+
+        - ``present``: present buckets in ``[lo, hi)``;
+        - ``imputed``: grid points ``g`` in ``[lo, nproc)`` with no present
+          bucket in ``[g, g + win_buckets)`` — model inputs that are a
+          forward-filled carry, a back-filled prefix or a literal 0;
+        - ``stale``: length of the run of non-present buckets ending at
+          ``hi - 1`` (0 when that bucket is present, ``span`` when none is);
+          ``stale * bucket_s`` bounds the newest sample's age from below.
+
+        The numbers describe the buckets as they stand at the call: a late
+        event accepted into a bucket >= ``nproc`` after an earlier grid
+        point already consumed that bucket shows as present.
+
+        Raises ValueError before the first full model window (``nproc <
+        model_win``) and when the span is no longer wholly in the ring (a
+        catch-up skip, or samples far ahead of the watermark, cleared the
+        slots of its oldest buckets). Duplicate ids are harmless, rows
+        follow the list order, an empty list launches nothing. Ring
+        positions are passed by value (legal between graph replays, not
+        captured)."""
+        assert self._dstate is None, "not inside a device_state block"
+        ids = None if sids is None else self._check_sids(sids)
+        L, Wb = self.model_win, self.win_buckets
+        if self.nproc < L:
+            raise ValueError(
+                f"no full model window yet: {self.nproc} of {L} grid points")
+        lo, span = self.nproc - L, L + Wb - 1
+        if max(self.head, self._cleared) - lo > self.G:
+            raise ValueError(
+                f"the window's buckets [{lo}, {lo + span}) are no longer "
+                f"wholly in the ring (G={self.G}, written up to bucket "
+                f"{max(self.head, self._cleared)})")
+        n = self.S if ids is None else int(ids.size)
+        out = torch.empty((n, self.C, 3), dtype=torch.int32,
+                          device=self.device)
+        if n == 0:
+            return out
+        if self._gpu:
+            dids = None if ids is None else \
+                torch.from_numpy(ids.astype(np.int32)).to(self.device)
+            hip.check(hip.load(hip.PREPROC).tskd_preproc_window_coverage(
+                hip.ptr(self.bcnt), self._bst, hip.ptr(dids), n, self.S,
+                self.C, self.G, self.nproc, L, Wb, self._bucket_floor,
+                hip.ptr(out), hip.stream_ptr()),
+                "tskd_preproc_window_coverage")
+            return out
+        bidx = (lo + np.arange(span)) % self.G
+        cnt = self.bcnt.numpy()[:, :, bidx]
+        pres = (cnt if ids is None else cnt[ids]) > 0        # (n, C, span)
+        pres[:, :, :min(max(self._bucket_floor - lo, 0), span)] = True
+        # present buckets per window [g, g + Wb): differences of a prefix sum
+        cs = np.zeros(pres.shape[:2] + (span + 1,), dtype=np.int64)
+        np.cumsum(pres, axis=-1, out=cs[:, :, 1:])
+        rev = pres[:, :, ::-1]
+        res = np.stack([
+            cs[:, :, -1],
+            (cs[:, :, Wb:] == cs[:, :, :L]).sum(-1),
+            np.where(rev.any(-1), rev.argmax(-1), span)], axis=-1)
+        out.copy_(torch.from_numpy(res.astype(np.int32)))
+        return out
+
     # ------------------------------------------------------------ warm restart
     def _geometry(self) -> dict:
         return {"C": self.C, "fs": self.fs, "bucket_s": self.bucket_s,
@@ -715,6 +791,7 @@ class StreamEngine:
         self._forced_ready = self._forced_ready or bool(snap.forced_ready)
         self.born[dst] = np.asarray(snap.born, dtype=np.int64)
         self._proc_floor = nproc - keep
+        self._bucket_floor = nproc
 
 
 class TriggerGraph:

@@ -18,7 +18,11 @@ from typing import Dict, Optional
 STREAM_STATES = ("active", "admitted_total", "evicted_total",
                  "rejected_total",
                  # warm restart: state files refused at start (cold starts)
-                 "restore_failed")
+                 "restore_failed",
+                 # coverage gate (serve --min-coverage): predictions withheld
+                 # since start, mean coverage of the last trigger's streams,
+                 # triggers whose window had left the ring (nothing withheld)
+                 "withheld_total", "coverage_mean", "coverage_unavailable")
 
 
 class StageTimer:

@@ -350,6 +350,84 @@ __global__ __launch_bounds__(256) void snapshot_streams_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// 1e. Window coverage: how much of the latest model window rests on samples.
+//     The window's L grid points [lo, lo+L) (lo = nproc - L) average buckets
+//     [lo, lo+span), span = L + W - 1. Bucket j of the span is PRESENT iff
+//     j < nfloor (below a restored engine's floor: state unknown, counted as
+//     present) or its count is > 0. Per (stream, channel) row, int32 x 3:
+//       present  present buckets in the span
+//       imputed  grid points i in [0, L) with no present bucket in [i, i+W)
+//       stale    run of non-present buckets ending at the span's last one
+// ---------------------------------------------------------------------------
+// One wave per row, grid-strided. Lane l loads the counts of span buckets
+// l, l+64, l+128 (stride BST floats, so packed and split rings both work;
+// the span wraps at most once: g0 < G and span <= G), all three loads before
+// the first use. Three ballots give the row's presence as a wave-uniform
+// 192-bit mask m[0..2]; present is three popcounts, stale a leading-zero
+// count down from bit span-1 (bits from span on are 0 by construction), and
+// for imputed lane l of round q tests bits [64q+l, 64q+l+W) — a funnel shift
+// of m[q], m[q+1] by l — then a ballot and a popcount. No LDS, no atomics;
+// lane 0 stores the three results. Positions arrive by value (no device
+// state block is read). Row offsets are 64-bit.
+#define COV_MAXSPAN 192
+
+__global__ __launch_bounds__(256) void window_coverage_kernel(
+    const float* __restrict__ bcnt, int BST, const int* __restrict__ sids,
+    int n, int S, int C, int G, int g0, int nfloor, int L, int W,
+    int* __restrict__ out)
+{
+    typedef unsigned long long u64;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
+    const long nwaves = (long)gridDim.x * blockDim.x / WAVE;
+    const int span = L + W - 1;
+    const u64 wmask = W >= 64 ? ~0ull : (1ull << W) - 1;
+    const long rows = (long)n * C;
+    for (long r = wave; r < rows; r += nwaves) {
+        const int k = (int)(r / C), c = (int)(r - (long)k * C);
+        const int s = sids ? sids[k] : k;
+        if ((unsigned)s >= (unsigned)S) continue;  // host range-checks too
+        const float* row = bcnt + ((long)s * C + c) * G * BST;
+        float v[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            // lanes past the span re-read its last bucket (masked below):
+            // an unconditional load keeps the three in flight together
+            int g = g0 + min(lane + WAVE * q, span - 1);
+            if (g >= G) g -= G;
+            v[q] = row[(long)g * BST];
+        }
+        u64 m[4];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const int j = lane + WAVE * q;
+            m[q] = __ballot((j < span) & ((j < nfloor) | (v[q] > 0.f)));
+        }
+        m[3] = 0;
+        const int present = __popcll(m[0]) + __popcll(m[1]) + __popcll(m[2]);
+        int top = -1;  // highest present bucket of the span
+        if (m[2]) top = 191 - __clzll(m[2]);
+        else if (m[1]) top = 127 - __clzll(m[1]);
+        else if (m[0]) top = 63 - __clzll(m[0]);
+        int imputed = 0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            // bits [64q + lane, 64q + lane + 64) of the mask
+            const u64 x = lane ? (m[q] >> lane) | (m[q + 1] << (WAVE - lane))
+                               : m[q];
+            imputed += __popcll(__ballot((lane + WAVE * q < L) &
+                                         ((x & wmask) == 0)));
+        }
+        if (lane == 0) {
+            int* o = out + r * 3;
+            o[0] = present;
+            o[1] = imputed;
+            o[2] = span - 1 - top;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // 2. Sliding-window average + ffill/bfill/zero-fill
 //    Processes proc grid points [phead, phead+np): window starting at grid j
 //    averages buckets [j, j+win_buckets). The fill is an order-dependent
@@ -989,6 +1067,31 @@ int tskd_preproc_restore_streams(const int* sids, int n, float* bsum,
     return launch_snapshot(true, sids, n, bsum, bcnt, proc, last_val, S, C, G,
                            bst, nproc, nbk, keep, (float*)in,
                            (hipStream_t)stream);
+}
+
+// Coverage of the model window ending at nproc: out (n, C, 3) int32 =
+// [present, imputed, stale] per row of the listed streams (sids null: all S,
+// n = S). -4: a shape or position the kernel does not cover (span above
+// COV_MAXSPAN or G, W outside [1, 64], nproc < L); -5: a stride other than
+// 1 or 2.
+int tskd_preproc_window_coverage(const float* bcnt, int bst, const int* sids,
+                                 int n, int S, int C, int G, long nproc, int L,
+                                 int W, long floor, int* out, void* stream) {
+    if (S <= 0 || C <= 0 || G <= 0 || L < 1 || W < 1 || W > 64) return -4;
+    const int span = L + W - 1;
+    if (span > COV_MAXSPAN || span > G || nproc < L) return -4;
+    if (bst != 1 && bst != 2) return -5;
+    if (!sids && n != S) return -4;
+    if (n <= 0) return 0;
+    const long lo = nproc - L;
+    long nfloor = floor - lo;  // span buckets below the restore floor
+    if (nfloor < 0) nfloor = 0;
+    if (nfloor > span) nfloor = span;
+    const long nthreads = (long)n * C * WAVE;  // one wave per row
+    hipLaunchKernelGGL(window_coverage_kernel, dim3(grid_for(nthreads, 256)),
+                       dim3(256), 0, (hipStream_t)stream, bcnt, bst, sids, n,
+                       S, C, G, (int)(lo % G), (int)nfloor, L, W, out);
+    return (int)hipGetLastError();
 }
 
 int tskd_preproc_window_fill(const float* bsum, const float* bcnt, float* proc,

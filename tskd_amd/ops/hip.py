@@ -41,6 +41,8 @@ SIGNATURES = {
                                           I, P, P],
         "tskd_preproc_restore_streams": [P, I, P, P, P, P, I, I, I, I, L, I,
                                          I, P, P],
+        "tskd_preproc_window_coverage": [P, I, P, I, I, I, I, L, I, I, L, P,
+                                         P],
         "tskd_preproc_window_fill": [P, P, P, P, I, I, I, L, I, I, P, I, P],
         "tskd_preproc_advance_state": [P, I, I, P],
         "tskd_preproc_window_gather": [P, P, I, I, I, I, I, I, I, I, L, P, I,
