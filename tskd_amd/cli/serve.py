@@ -54,8 +54,25 @@ class FusedServer:
                  rank: int = 0, world: int = 1,
                  pipelined: bool = False, evict_idle_s: float = 0.0,
                  state_path: Optional[str] = None, snapshot_every: int = 1,
-                 min_coverage: float = 0.0):
+                 min_coverage: float = 0.0,
+                 explain_above: Optional[float] = None,
+                 explain_baseline: str = "hold"):
         self.cfg = cfg
+        # channel attribution (opt-in; None = off, so that a threshold of 0
+        # explains every prediction): a persisted prediction with risk >=
+        # explain_above is attributed in the same trigger, before
+        # the ring moves (se.attribute_latest), and its response-topic JSON
+        # carries the per-channel occlusion deltas. Choosing the streams
+        # needs the scores on the host, which the pipelined mode defers.
+        self.explain_above = None if explain_above is None \
+            else float(explain_above)
+        self.explain_baseline = explain_baseline
+        if explain_baseline not in ("hold", "zero"):
+            raise ValueError(f"explain_baseline={explain_baseline!r} is "
+                             f"neither 'hold' nor 'zero'")
+        if self.explain_above is not None and pipelined:
+            raise ValueError("explain_above needs the scores on the host in "
+                             "the trigger that made them: not with pipelined")
         # coverage gate (opt-in; 0 = off): a stream whose latest model window
         # holds less than this fraction of inputs that rest on samples (the
         # rest being a carried, back-filled or zero value: se.coverage) is
@@ -455,9 +472,37 @@ class FusedServer:
                 sum(q[i] for i, b in enumerate(base) if b) / sum(base))
         return q, [b and not h for b, h in zip(base, held)]
 
+    def _explain(self, vals, slots) -> Dict[int, str]:
+        """Attribute the predictions with risk >= explain_above in one call:
+        {position in ``vals``: the response's attribution fragment}, deltas
+        over the channels the config names, in its order. ``slots`` are the
+        ring slots of ``vals``. Empty when the engine refuses (a restored
+        ring's window reaches below the restore floor)."""
+        pick = [j for j in range(len(slots))
+                if float(vals[j]) >= self.explain_above]
+        if not pick:
+            return {}
+        age = torch.full((self.se.S, 1), 65.0, device=self.se.device)
+        age[:self._age_dev.shape[0]] = self._age_dev
+        try:
+            out = self.se.attribute_latest(
+                self.me, [slots[j] for j in pick], age=age,
+                baseline=self.explain_baseline, apply_sigmoid=True).cpu()
+        except ValueError as e:
+            log.warning("attribution unavailable: %s", e)
+            return {}
+        delta = (out[:, :1] - out[:, 1:1 + self.cfg.n_channels]).tolist()
+        g = self.timer.gauges
+        g["explained_total"] = g.get("explained_total", 0) + len(pick)
+        return {j: ', "attribution": {"baseline": "%s", "delta": [%s]}' % (
+                    self.explain_baseline,
+                    ", ".join(f"{d:.6f}" for d in delta[r]))
+                for r, j in enumerate(pick)}
+
     def _persist(self, probs, t_us: int, pids, mask=None,
                  imputed=None) -> None:
         q = None
+        slots = range(len(pids))
         if imputed is not None:
             q, mask = self._coverage_gate(imputed, len(pids), mask)
             if not any(mask):
@@ -468,9 +513,12 @@ class FusedServer:
             probs = probs.reshape(-1)[:len(pids)][
                 torch.tensor(keep, dtype=torch.long, device=probs.device)]
             pids = [pids[i] for i in keep]
+            slots = keep
             if q is not None:
                 q = q[keep]
         n = len(pids)
+        attr = self._explain(probs.reshape(-1)[:n].cpu(), slots) \
+            if self.explain_above is not None else {}
         if self.store is not None:
             # the mmap store is multi-process safe: each rank persists
             # its own shard directly (no gather needed for durability)
@@ -483,7 +531,8 @@ class FusedServer:
                 cov = "" if q is None else f', "coverage": {q[i]:.4f}'
                 self.producer.produce(
                     self.response_topic, pid,
-                    f'{{"t_us": {t_us}, "risk": {float(vals[i]):.6f}{cov}}}')
+                    f'{{"t_us": {t_us}, "risk": {float(vals[i]):.6f}{cov}'
+                    f'{attr.get(i, "")}}}')
 
     def flush(self) -> None:
         """Persist the deferred trigger (pipelined mode; call on shutdown
@@ -656,9 +705,24 @@ def main(argv=None) -> None:
                          "whose latest model window has less than this "
                          "fraction of inputs resting on samples, the rest "
                          "being carried, back-filled or zero (0 = off)")
+    ap.add_argument("--explain-above", type=float, default=None, metavar="R",
+                    help="channel attribution: a published prediction with "
+                         "risk >= R carries per-channel occlusion deltas "
+                         "(score minus the score with that channel held "
+                         "flat or zeroed) in the response topic (off "
+                         "unless given)")
+    ap.add_argument("--explain-baseline", default="hold",
+                    choices=["hold", "zero"],
+                    help="with --explain-above: what replaces a channel, "
+                         "its oldest point in the window (a lead that fell "
+                         "off) or 0 (a channel that never arrived)")
     args = ap.parse_args(argv)
     if not 0.0 <= args.min_coverage <= 1.0:
         ap.error("--min-coverage must lie in [0, 1]")
+    if args.explain_above is not None and args.pipelined:
+        ap.error("--explain-above cannot be combined with --pipelined: "
+                 "choosing the streams needs the scores on the host in the "
+                 "trigger that made them, and --pipelined defers them")
     if args.state_dir and args.poll_thread:
         ap.error("--state-dir cannot be combined with --poll-thread: the "
                  "poll thread owns the consumer, so the bus positions run "
@@ -685,7 +749,9 @@ def main(argv=None) -> None:
                       rank=rank, world=world, pipelined=args.pipelined,
                       evict_idle_s=args.evict_idle_s,
                       snapshot_every=args.snapshot_every,
-                      min_coverage=args.min_coverage)
+                      min_coverage=args.min_coverage,
+                      explain_above=args.explain_above,
+                      explain_baseline=args.explain_baseline)
     if args.state_dir:
         os.makedirs(args.state_dir, exist_ok=True)
         srv.state_path = state_file(args.state_dir, rank, world)

@@ -471,6 +471,92 @@ class StreamEngine:
             self.proc, self.G, self.nproc, self._dstate_ptr(),
             self._dstate_gather_extra, age, apply_sigmoid)
 
+    # ------------------------------------------------------------- attribution
+    def attribute_latest(self, model_engine, sids=None,
+                         age: Optional[torch.Tensor] = None,
+                         baseline: str = "hold",
+                         apply_sigmoid: bool = True) -> torch.Tensor:
+        """Occlusion scores of the listed streams' latest model windows (all
+        S streams when ``sids`` is None): fp32 ``(n, C + 1)``, one row per
+        listed id. Column 0 is the score of the window as it stands (what
+        ``score_latest`` returns); column k is the score with channel k - 1
+        replaced for all ``model_win`` points by a constant: the window's
+        oldest point (``baseline="hold"``: a flat line, the forward-fill
+        carry of a lead that fell off ten minutes ago) or +0.0 (``"zero"``:
+        the ``fillna(0)`` of a channel that never arrived). ``out[:, 0] -
+        out[:, c + 1]`` is channel c's attribution: positive when its actual
+        course raised the score. Occlusion against the pipeline's own two
+        imputation baselines, not a causal claim.
+
+        ``age``: ``(S, 1)`` / ``(S,)`` indexed by stream id, or None.
+        Duplicate ids are harmless, an empty list launches nothing. Runs the
+        fused kernel when ``model_engine.supports_attribution(C)``, else
+        :meth:`attribute_reference` in fp32. The ring position is passed by
+        value (legal between graph replays, not captured). ValueError: an id
+        outside [0, S), an unknown baseline, no full model window yet, or a
+        window that reaches below the restore floor."""
+        assert self._dstate is None, "not inside a device_state block"
+        if not model_engine.supports_attribution(self.C):
+            return self.attribute_reference(model_engine, sids, age, baseline,
+                                            apply_sigmoid)
+        ids, age = self._attribution_args(sids, age, baseline)
+        dids = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+        return model_engine.attribute_ring(
+            self.proc, self.G, self.nproc, dids, age, baseline, apply_sigmoid)
+
+    def _attribution_args(self, sids, age, baseline):
+        """Checked arguments of an attribution call: (int64 ids, age rows of
+        those ids as (n, 1) or None)."""
+        from tskd_amd.ops import BASELINES
+        assert self.model_win == 120
+        if baseline not in BASELINES:
+            raise ValueError(f"baseline {baseline!r} not in {list(BASELINES)}")
+        ids = np.arange(self.S, dtype=np.int64) if sids is None \
+            else self._check_sids(sids)
+        if self.nproc < self.model_win:
+            raise ValueError(f"no full model window yet: {self.nproc} of "
+                             f"{self.model_win} grid points")
+        self._check_floor(self.model_win)
+        if age is not None:
+            age = age.reshape(self.S, 1)[
+                torch.from_numpy(ids).to(age.device)]
+        return ids, age
+
+    def attribute_reference(self, model_engine, sids=None,
+                            age: Optional[torch.Tensor] = None,
+                            baseline: str = "hold",
+                            apply_sigmoid: bool = True,
+                            dtype: torch.dtype = torch.float32
+                            ) -> torch.Tensor:
+        """:meth:`attribute_latest` from existing pieces only: gather the
+        windows, copy each listed stream's C + 1 times with one channel
+        overwritten per copy, score the copies as independent one-window
+        sequences with ``model_engine.forward``. The fallback for engines
+        the kernel does not cover (CPU, MyCNN2/3) and the kernel's oracle:
+        with ``dtype=torch.bfloat16`` the windows are the time-last bf16
+        ones the serving path scores, and the constant overwrites bf16
+        values, which is what converting a flat fp32 channel gives."""
+        ids, age = self._attribution_args(sids, age, baseline)
+        timelast = dtype == torch.bfloat16
+        w = self.windows(batch=1, dtype=dtype, timelast=timelast)
+        x = w[torch.from_numpy(ids).to(w.device)]       # (n, 1, ...)
+        if timelast:
+            x = x.transpose(-1, -2)                      # (n, 1, C, WIN) view
+        n, C = len(ids), self.C
+        v = x.unsqueeze(1).repeat(1, C + 1, 1, 1, 1)     # (n, C+1, 1, C, WIN)
+        for k in range(1, C + 1):
+            v[:, k, 0, k - 1, :] = 0.0 if baseline == "zero" \
+                else x[:, 0, k - 1, :1]
+        if timelast:
+            v = v.transpose(-1, -2).contiguous()
+        v = v.reshape(n * (C + 1), 1, *v.shape[-2:])
+        if age is not None:
+            age = age.to(torch.float32).repeat_interleave(C + 1, dim=0)
+        if n == 0:
+            return torch.empty(0, C + 1, device=self.device)
+        out = model_engine.forward(v, age, apply_sigmoid=apply_sigmoid)
+        return out.reshape(n, C + 1).to(torch.float32)
+
     @property
     def ready(self) -> bool:
         """A full model window exists (>= 600 s + 180 s of data SINCE THE

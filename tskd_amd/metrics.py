@@ -22,7 +22,10 @@ STREAM_STATES = ("active", "admitted_total", "evicted_total",
                  # coverage gate (serve --min-coverage): predictions withheld
                  # since start, mean coverage of the last trigger's streams,
                  # triggers whose window had left the ring (nothing withheld)
-                 "withheld_total", "coverage_mean", "coverage_unavailable")
+                 "withheld_total", "coverage_mean", "coverage_unavailable",
+                 # channel attribution (serve --explain-above): predictions
+                 # that were attributed since start
+                 "explained_total")
 
 
 class StageTimer:

@@ -37,6 +37,9 @@ def _age_ptr(age: Optional[torch.Tensor], s: int, n: int) -> Tuple:
 
 TLAST_SLACK = 256  # trailing elements the timelast conv kernel may overread
 
+# channel-attribution baselines -> OCCLUDE_* in csrc/mycnn_kernels.hip
+BASELINES = {"hold": 0, "zero": 1}
+
 
 def alloc_windows(s: int, n: int, cin: int, win: int = 120,
                   timelast: bool = False, dtype=torch.bfloat16,
@@ -166,6 +169,47 @@ class MyCNNEngine:
             int(end_extra), age_ptr, hip.ptr(out), hip.ptr(self.wpack),
             hip.ptr(self.bfrag), self.age_eps, int(apply_sigmoid),
             self.variant, hip.stream_ptr()), "tskd_serve_tail_fwd")
+        return out
+
+    def supports_attribution(self, n_channels: int) -> bool:
+        """True when :meth:`attribute_ring` applies: the coverage of
+        :meth:`score_ring`."""
+        return self.supports_fused_tail(n_channels)
+
+    def attribute_ring(self, proc: torch.Tensor, G: int, end: int, sids,
+                       age: Optional[torch.Tensor] = None,
+                       baseline: str = "hold",
+                       apply_sigmoid: bool = False) -> torch.Tensor:
+        """Occlusion scores of the listed streams' latest windows straight
+        from a StreamEngine's (S, C, G) fp32 ``proc`` ring, in ONE kernel:
+        (n, C + 1) fp32, column 0 the score of the window ending at ``end``
+        as :meth:`score_ring` gives it, column k the score with channel
+        k - 1 replaced for all 120 points by a constant — the window's
+        oldest point (``baseline="hold"``: a flat line, what the forward-fill
+        carry makes of a lead that fell off) or +0.0 (``"zero"``: a channel
+        that never arrived). ``sids``: int32 device tensor of n stream ids
+        (rows follow it, duplicates are harmless, an id outside [0, S) is
+        skipped and its row left unwritten); ``age``: (n,) / (n, 1) per
+        listed stream, or None. The ring position is passed by value: legal
+        between graph replays, not captured. Raises for variants the kernel
+        does not cover and for an unknown baseline."""
+        if baseline not in BASELINES:
+            raise ValueError(f"baseline {baseline!r} not in {list(BASELINES)}")
+        assert proc.dim() == 3 and proc.dtype == torch.float32 \
+            and proc.is_contiguous() and proc.shape[2] == G
+        assert sids.dtype == torch.int32 and sids.dim() == 1 \
+            and sids.is_contiguous() and sids.device == proc.device
+        s, c, n = proc.shape[0], proc.shape[1], sids.numel()
+        out = torch.empty(n, c + 1, dtype=torch.float32, device=proc.device)
+        if n == 0:
+            return out
+        age_ptr, age = _age_ptr(
+            None if age is None else age.reshape(n, 1), n, 1)
+        hip.check(hip.load(hip.MYCNN).tskd_serve_tail_occlude_fwd(
+            hip.ptr(proc), s, c, int(G), int(end), hip.ptr(sids), n, age_ptr,
+            BASELINES[baseline], hip.ptr(out), hip.ptr(self.wpack),
+            hip.ptr(self.bfrag), self.age_eps, int(apply_sigmoid),
+            self.variant, hip.stream_ptr()), "tskd_serve_tail_occlude_fwd")
         return out
 
     def forward(self, x: torch.Tensor, age: Optional[torch.Tensor] = None,

@@ -39,6 +39,10 @@
 //      kernel — window gather from the fp32 ring + 1b's conv + ONE LSTM step
 //      + head. MyCNN5/MyCNN4 (even CIN).
 //
+//   4. serve_tail_occlude_kernel: channel attribution — kernel 3 on C + 1
+//      variants of a listed stream's window (one channel held flat or zeroed
+//      per variant), the ring window read once per stream.
+//
 //   debug_mfma_kernel: one 16x16x32 bf16 MFMA tile, the fragment-map ground
 //   truth for the tests.
 //
@@ -760,6 +764,338 @@ __global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Kernel 4 (channel attribution): occlusion scores of listed streams' latest
+// windows straight from the ring. Variant 0 is the window as it stands (what
+// serve_tail_kernel scores); variant k = 1..CIN has channel k-1 replaced for
+// all 120 t by one constant: +0.0 (OCCLUDE_ZERO, "the channel never
+// arrived") or the window's oldest point (OCCLUDE_HOLD, "the lead fell off
+// ten minutes ago": the forward-fill carry). out is (n, CIN + 1).
+//
+// Schedule: the wave's pair of images is two variants of one stream, so the
+// CIN + 1 = 11 variants take 6 rounds (the twelfth image is skipped). One
+// wave per (listed stream, round) item, ONE flat grid-stride loop: a
+// workgroup's 4 waves take consecutive rounds, mostly of the same stream, so
+// HBM sees a stream's 4.8 KB window once and the other rounds read it from
+// L1/L2. A round reads the window once (serve_tail_kernel's coalesced read
+// and unwrap), packs it to bf16 pairs in 10 VGPRs and stages both images
+// from those: the constant replaces fp32 ring values before the RNE
+// conversion, which for one value is the conversion of that value, so only
+// the occluded channel's half-word of a packed dword changes. conv1,
+// conv_tail and the LSTM step are serve_tail_kernel's, operation for
+// operation, and weights, biases and B fragments stay in registers across
+// the loop. Keeping the packed window in registers across a stream's 6
+// rounds (a round loop nested in the stream loop) was built first and
+// spilled 56 B per lane at 128 VGPRs; the flat loop has serve_tail_kernel's
+// shape and does not (126 VGPRs, MyCNN5).
+//
+// Tail<G> below holds serve_tail_kernel's pieces as functions. That kernel
+// keeps its own in-place copies: built from these functions it computes the
+// same values but the compiler allocates 128 instead of 123 VGPRs and
+// schedules it differently (as with load_bfrags in kernel 1b), and its
+// measured schedule is the one the serving step is tuned on.
+// ---------------------------------------------------------------------------
+#define OCCLUDE_HOLD 0
+#define OCCLUDE_ZERO 1
+
+template <class G>
+struct Tail {
+    static_assert(G::CIN % 2 == 0, "packed staging needs an even CIN");
+    static_assert(G::XTSZ % 8 == 0 && G::XTN % 2 == 0, "");
+    static constexpr int LIN = G::LIN;
+    static constexpr int CD  = G::CIN / 2;    // dwords per time-major row
+    static constexpr int XTD = G::XTSZ / 2;   // padded image, dwords
+    static constexpr int NT  = (G::L + WAVE - 1) / WAVE;  // t's per lane
+    // pool/conv2 scratch and the feature row live in window a's image, which
+    // is dead once the MFMA loop has read it (and is restaged every pair)
+    static_assert(4 * G::P1 + G::C2 + LIN <= G::XTN / 2, "scratch > image");
+
+    // B fragments and LSTM / head rows (lane = gate row), once per wave. No
+    // whh blocks.
+    bf16x8 bfr[G::KSTEPS];
+    float wih1[LIN], wih2[16], outw[16];
+    float bl1, bl2, outb;
+
+    __device__ __forceinline__ void load(const float* __restrict__ wpack,
+                                         const unsigned short* bfrag,
+                                         int lane) {
+        load_bfrags<G>(bfrag, lane, bfr);
+        bl1 = wpack[G::OBL1 + lane];
+        bl2 = wpack[G::OBL2 + lane];
+        #pragma unroll
+        for (int i = 0; i < LIN; ++i)
+            wih1[i] = wpack[G::OWIH1 + lane * LIN + i];
+        #pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            wih2[i] = wpack[G::OWIH2 + lane * 16 + i];
+            outw[i] = wpack[G::OOUTW + i];   // uniform address
+        }
+        outb = wpack[G::OOUTB];
+    }
+
+    // Per-lane byte offsets into a channel row for t = lane + 64*h; the
+    // window starts at ring slot `start` and wraps at most once.
+    static __device__ __forceinline__ void ring_offsets(
+        int start, int ring, int lane, unsigned int (&goff)[NT])
+    {
+        #pragma unroll
+        for (int h = 0; h < NT; ++h) {
+            unsigned int gi = start + lane + h * WAVE;
+            if (gi >= (unsigned int)ring) gi -= ring;   // at most one wrap
+            goff[h] = gi * 4u;
+        }
+    }
+
+    // Stream s's window as packed bf16 pairs, pk[h][c/2] = channels c, c+1
+    // at t = lane + 64*h (RNE): uniform row base + 32-bit lane offset, all
+    // loads issued first. Not live: the all-zero window.
+    static __device__ __forceinline__ void ring_load(
+        const float* __restrict__ proc, long s, int ring,
+        const unsigned int (&goff)[NT], int lane, bool live,
+        unsigned int (&pk)[NT][CD])
+    {
+        const char* pr = (const char*)(proc + s * ((long)G::CIN * ring));
+        float v[NT][G::CIN];
+        #pragma unroll
+        for (int h = 0; h < NT; ++h) {
+            #pragma unroll
+            for (int c = 0; c < G::CIN; ++c) v[h][c] = 0.f;
+        }
+        if (live) {
+            #pragma unroll
+            for (int h = 0; h < NT; ++h) {
+                if (lane + h * WAVE < G::L) {
+                    #pragma unroll
+                    for (int c = 0; c < G::CIN; ++c)
+                        v[h][c] = *(const float*)(pr + (long)c * ring * 4
+                                                  + goff[h]);
+                }
+            }
+        }
+        #pragma unroll
+        for (int h = 0; h < NT; ++h) {
+            #pragma unroll
+            for (int c = 0; c < G::CIN; c += 2)
+                pk[h][c >> 1] =
+                    (unsigned int)f32_to_bf16(v[h][c]) |
+                    ((unsigned int)f32_to_bf16(v[h][c + 1]) << 16);
+        }
+    }
+
+    // Packed window -> the time-major image xt[t*CIN + c] (row stride CD
+    // dwords); the zeroed tail past t = L-1 is never written.
+    static __device__ __forceinline__ void image_store(
+        unsigned int* xt, int lane, const unsigned int (&pk)[NT][CD])
+    {
+        #pragma unroll
+        for (int h = 0; h < NT; ++h) {
+            if (lane + h * WAVE < G::L) {
+                #pragma unroll
+                for (int cd = 0; cd < CD; ++cd)
+                    xt[(lane + h * WAVE) * CD + cd] = pk[h][cd];
+            }
+        }
+    }
+
+    static __device__ __forceinline__ void c1_store(
+        float* c1w, const float* b1, const f32x4& acc, int mt, int lane)
+    {
+        const int c = lane & 15;
+        if (c < 4) {
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = mt * 16 + (lane >> 4) * 4 + r;
+                if (row < G::C1) c1w[c * G::C1 + row] = acc[r] + b1[c];
+            }
+        }
+    }
+
+    // conv1 of the two images: kernel 1b's even-CIN MFMA im2col loop, the
+    // pair's chains interleaved, one c1 row set per image.
+    __device__ __forceinline__ void conv1_pair(
+        const unsigned int* xta, const unsigned int* xtb, float* c1a,
+        float* c1b, const float* b1, int lane) const
+    {
+        #pragma unroll 1
+        for (int mt = 0; mt < G::MTILES; ++mt) {
+            f32x4 acca = {0.f, 0.f, 0.f, 0.f};
+            f32x4 accb = {0.f, 0.f, 0.f, 0.f};
+            #pragma unroll
+            for (int st = 0; st < G::KSTEPS; ++st) {
+                // even element offset: aligned dwords are fragment dwords
+                const int bd = ((mt * 16 + (lane & 15)) * G::CIN + st * 32
+                                + (lane >> 4) * 8) / 2;
+                BU aa, ab;
+                #pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    aa.d[q] = xta[bd + q];
+                    ab.d[q] = xtb[bd + q];
+                }
+                acca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    aa.v, bfr[st], acca, 0, 0, 0);
+                accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    ab.v, bfr[st], accb, 0, 0, 0);
+            }
+            c1_store(c1a, b1, acca, mt, lane);
+            c1_store(c1b, b1, accb, mt, lane);
+        }
+    }
+
+    // One LSTM step from zero state + head on the feature row fw; lane 0
+    // reads age[ai] (age may be null) and writes out[oi].
+    __device__ __forceinline__ void lstm_step(
+        const float* fw, int lane, const float* __restrict__ age, long ai,
+        float* __restrict__ out, long oi, float age_eps,
+        int apply_sigmoid) const
+    {
+        const int unit = lane & 15;
+        const bool is_cell_gate = (lane >= 32 && lane < 48);
+        float h1v[16], h2v[16];
+        float ga = bl1, gb = 0.f;
+        #pragma unroll
+        for (int i = 0; i < LIN; i += 2) {
+            ga = fmaf(wih1[i], fw[i], ga);
+            if (i + 1 < LIN) gb = fmaf(wih1[i + 1], fw[i + 1], gb);
+        }
+        float g = ga + gb;
+        float a = is_cell_gate ? tanhf_(g) : sigmoidf_(g);
+        {
+            const float iu = __shfl(a, unit);
+            const float gu = __shfl(a, unit + 32);
+            const float ou = __shfl(a, unit + 48);
+            const float h = ou * tanhf_(iu * gu);
+            #pragma unroll
+            for (int u = 0; u < 16; ++u) h1v[u] = __shfl(h, u);
+        }
+        ga = bl2; gb = 0.f;
+        #pragma unroll
+        for (int u = 0; u < 16; u += 2) {
+            ga = fmaf(wih2[u], h1v[u], ga);
+            gb = fmaf(wih2[u + 1], h1v[u + 1], gb);
+        }
+        g = ga + gb;
+        a = is_cell_gate ? tanhf_(g) : sigmoidf_(g);
+        {
+            const float iu = __shfl(a, unit);
+            const float gu = __shfl(a, unit + 32);
+            const float ou = __shfl(a, unit + 48);
+            const float h = ou * tanhf_(iu * gu);
+            #pragma unroll
+            for (int u = 0; u < 16; ++u) h2v[u] = __shfl(h, u);
+        }
+        if (lane == 0) {
+            float y = outb;
+            #pragma unroll
+            for (int u = 0; u < 16; ++u) y = fmaf(outw[u], h2v[u], y);
+            const float ag = age ? age[ai] : 0.f;
+            y *= fmaxf(fmaf(ag, age_eps, 1.0f), 0.0f);
+            if (apply_sigmoid) y = sigmoidf_(y);
+            out[oi] = y;
+        }
+        wave_sync();  // feature-row reads done before the next tail's store
+    }
+};
+
+template <class G>
+__global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_occlude_kernel(
+    const float* __restrict__ proc,   // (S, CIN, ring) fp32 processed ring
+    const int* __restrict__ sids,     // (n) stream ids
+    const float* __restrict__ age,    // (n) or nullptr
+    float* __restrict__ out,          // (n, CIN + 1)
+    const float* __restrict__ wpack,
+    const unsigned short* __restrict__ bfrag,  // [KSTEPS][64][8] bf16 bits
+    int S, int n, int ring, long end, int baseline, float age_eps,
+    int apply_sigmoid)
+{
+    using T = Tail<G>;
+    constexpr int NV = G::CIN + 1;    // variants per stream
+    __shared__ float lds_w[G::NW];
+    __shared__ unsigned int lds_xt[WG_WAVES][2][T::XTD];
+    __shared__ float lds_c1[WG_WAVES][2][4 * G::C1];
+
+    for (int i = threadIdx.x; i < G::NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const float* b1 = lds_w + G::OB1;
+    unsigned int* xta = lds_xt[wave][0];
+    unsigned int* xtb = lds_xt[wave][1];
+    float* c1a = lds_c1[wave][0];
+    float* c1b = lds_c1[wave][1];
+    float* p1w = (float*)xta;
+    float* c2w = p1w + 4 * G::P1;
+    float* fw = c2w + G::C2;
+
+    T tw;
+    tw.load(wpack, bfrag, lane);
+
+    // the launcher guarantees L <= end and L <= ring: a full window
+    const int start = (int)((end - G::L) % ring);
+    for (int i = G::XTN / 2 + lane; i < T::XTD; i += WAVE)
+        xta[i] = xtb[i] = 0u;
+    unsigned int goff[T::NT];
+    T::ring_offsets(start, ring, lane, goff);
+
+    // Image of variant k from the packed window: channel occ = k - 1 (none
+    // for k = 0) holds the baseline's bf16 bits `ins` in its half-word of
+    // dword occ / 2. occ, keep and ins are uniform.
+    auto stage = [&](unsigned int* xt, const unsigned int (&pk)[T::NT][T::CD],
+                     const unsigned int (&pk0)[T::CD], int k) {
+        const int occ = k - 1;
+        const bool hi = occ & 1;
+        unsigned int base = 0u;
+        if (baseline == OCCLUDE_HOLD) {
+            #pragma unroll
+            for (int cd = 0; cd < T::CD; ++cd)
+                if (cd == (occ >> 1)) base = pk0[cd];
+        }
+        const unsigned int keep = hi ? 0x0000ffffu : 0xffff0000u;
+        const unsigned int ins = hi ? (base & 0xffff0000u) : (base & 0xffffu);
+        unsigned int q[T::NT][T::CD];
+        #pragma unroll
+        for (int h = 0; h < T::NT; ++h) {
+            #pragma unroll
+            for (int cd = 0; cd < T::CD; ++cd)
+                q[h][cd] = (occ >= 0 && cd == (occ >> 1))
+                    ? ((pk[h][cd] & keep) | ins) : pk[h][cd];
+        }
+        T::image_store(xt, lane, q);
+    };
+
+    // One item = one round of one listed stream = variants ka, ka + 1.
+    constexpr int NR = (NV + 1) / 2;
+    for (long item = blockIdx.x * WG_WAVES + wave; item < (long)n * NR;
+         item += (long)gridDim.x * WG_WAVES) {
+        const long i = item / NR;
+        const int ka = (int)(item % NR) * 2, kb = ka + 1;
+        const bool hasb = kb < NV;
+        // uniform: say so, so the ring row base is scalar
+        const long s = __builtin_amdgcn_readfirstlane(sids[i]);
+        if (s < 0 || s >= S) continue;    // the host refuses these ids
+        unsigned int pk[T::NT][T::CD], pk0[T::CD];
+        T::ring_load(proc, s, ring, goff, lane, true, pk);
+        // the window's oldest point, t = 0, is lane 0's first row
+        #pragma unroll
+        for (int cd = 0; cd < T::CD; ++cd)
+            pk0[cd] = __builtin_amdgcn_readfirstlane(pk[0][cd]);
+        stage(xta, pk, pk0, ka);
+        stage(xtb, pk, pk0, hasb ? kb : 0);
+        wave_sync();
+
+        tw.conv1_pair(xta, xtb, c1a, c1b, b1, lane);
+        wave_sync();  // both images are dead from here: scratch may land
+        conv_tail<G, true>(lane, lds_w, c1a, p1w, c2w, fw, 0);
+        tw.lstm_step(fw, lane, age, i, out, i * NV + ka, age_eps,
+                     apply_sigmoid);
+        if (hasb) {
+            conv_tail<G, true>(lane, lds_w, c1b, p1w, c2w, fw, 0);
+            tw.lstm_step(fw, lane, age, i, out, i * NV + kb, age_eps,
+                         apply_sigmoid);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Debug: one 16x16x32 bf16 MFMA tile (fragment-map ground truth for tests)
 // ---------------------------------------------------------------------------
 __global__ void debug_mfma_kernel(const unsigned short* __restrict__ A,
@@ -863,11 +1199,56 @@ int launch_serve_tail(const float* proc, int S, int C, int ring, long end_in,
     }
 }
 
+// Channel attribution: serve_tail's coverage and codes; a window end before
+// the first full window is -5 as well, an unknown baseline -7.
+template <class G>
+int launch_serve_tail_occlude(const float* proc, int S, int C, int ring,
+                              long end, const int* sids, int n,
+                              const float* age, int baseline, float* out,
+                              const float* wpack, const void* bfrag,
+                              float age_eps, int apply_sigmoid,
+                              hipStream_t stream) {
+    if constexpr (G::CIN % 2 != 0) {
+        return SERVE_TAIL_UNSUPPORTED;
+    } else {
+        if (C != G::CIN) return SERVE_TAIL_UNSUPPORTED;
+        if (ring < G::L || ring > (1 << 29) || end < G::L) return -5;
+        if (baseline != OCCLUDE_HOLD && baseline != OCCLUDE_ZERO) return -7;
+        if (!bfrag) return -2;
+        if (n <= 0) return 0;
+        // one wave per (stream, round of two variants)
+        const long items = (long)n * ((G::CIN + 2) / 2);
+        const int g1 = (int)((items < 4 * 8192L ? items : 4 * 8192L)
+                             + WG_WAVES - 1) / WG_WAVES;
+        hipLaunchKernelGGL((serve_tail_occlude_kernel<G>), dim3(g1),
+                           dim3(WG_THREADS), 0, stream, proc, sids, age, out,
+                           wpack, (const unsigned short*)bfrag, S, n, ring,
+                           end, baseline, age_eps, apply_sigmoid);
+        return (int)hipGetLastError();
+    }
+}
+
 }  // namespace
 
 extern "C" {
 
 // variant (everywhere below): 0 = MyCNN5, 1 = MyCNN2/3, 2 = MyCNN4
+
+// Occlusion scores (n, C + 1) of the listed streams' latest windows ending at
+// `end` in the (S, C, G) fp32 ring; baseline 0 = hold, 1 = zero; age is (n)
+// or null.
+int tskd_serve_tail_occlude_fwd(const float* proc, int S, int C, int G,
+                                long end, const int* sids, int n,
+                                const float* age, int baseline, float* out,
+                                const float* wpack, const void* bfrag,
+                                float age_eps, int apply_sigmoid, int variant,
+                                void* stream) {
+    return dispatch_variant(variant, [&](auto g) {
+        return launch_serve_tail_occlude<typename decltype(g)::type>(
+            proc, S, C, G, end, sids, n, age, baseline, out, wpack, bfrag,
+            age_eps, apply_sigmoid, (hipStream_t)stream);
+    });
+}
 
 // Window gather + conv + one LSTM step + head from the (S, C, G) fp32 ring;
 // end = dstate ? dstate[1] + end_extra : end_in (as in the window gather).

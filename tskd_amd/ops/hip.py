@@ -25,6 +25,8 @@ U64 = ctypes.c_ulonglong
 SIGNATURES = {
     MYCNN: {
         "tskd_serve_tail_fwd": [P, I, I, I, L, P, I, P, P, P, P, F, I, I, P],
+        "tskd_serve_tail_occlude_fwd": [P, I, I, I, L, P, I, P, I, P, P, P, F,
+                                        I, I, P],
         "tskd_conv_fwd": [P, I, I, P, P, P, I, I, P],
         "tskd_lstm_head_fwd": [P, P, P, P, I, I, F, I, I, P],
         "tskd_debug_mfma16x16x32": [P, P, P, P],
