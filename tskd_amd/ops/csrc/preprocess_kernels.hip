@@ -113,9 +113,13 @@ __global__ void ingest_dense_kernel(
                 // EXCEPT for the very last bucket of the whole tensor,
                 // where the <= 14 B over-read would pass the allocation:
                 // that one task floors the chunk count and takes the
-                // scalar tail. The masked head read-back (<= 14 B before
-                // the bucket) stays inside the raw tensor for every bucket
-                // but (0,0,0), which is 16 B-aligned (mis = 0).
+                // scalar tail. When mis + bucket_len < 8 the floor is 0
+                // chunks and the tail is the whole bucket: it starts at
+                // sample 0, never before it. The masked head read-back
+                // (<= 14 B before the bucket) stays inside the raw tensor
+                // for every bucket but (0,0,0), where it stays inside the
+                // aligned 16 B chunk that holds the tensor's first sample
+                // (mis = 0 when the tensor starts its allocation).
                 const bool at_end = s == S - 1 && cin == CIN - 1 &&
                                     b == NB - 1;
                 const int nch = (mis + bucket_len + (at_end ? 0 : 7)) / 8;
@@ -151,7 +155,8 @@ __global__ void ingest_dense_kernel(
                     }
                 }
                 if (at_end)
-                    for (int i = nch * 8 - mis + lane; i < bucket_len;
+                    for (int i = max(nch * 8 - mis, 0) + lane;
+                         i < bucket_len;
                          i += ING_GL) {  // tensor-final bucket only
                         const float f = bf16_to_f32(su[i]);
                         if (!isnan(f)) { sum += f; cnt += 1.f; }
