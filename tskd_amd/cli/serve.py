@@ -56,8 +56,22 @@ class FusedServer:
                  state_path: Optional[str] = None, snapshot_every: int = 1,
                  min_coverage: float = 0.0,
                  explain_above: Optional[float] = None,
-                 explain_baseline: str = "hold"):
+                 explain_baseline: str = "hold", reload_check: int = 0,
+                 reload_max_shift: Optional[float] = None):
         self.cfg = cfg
+        # hot-reload vetting (opt-in; 0 = off): before a changed checkpoint
+        # goes live, the last reload_check triggers of the live ready slots
+        # are scored from the ring under the current and the candidate model
+        # (se.score_history) and the shift of the scores is exported; with
+        # reload_max_shift a candidate that moves any of them further, or
+        # gives a non-finite one, is refused
+        self.reload_check = int(reload_check)
+        self.reload_max_shift = None if reload_max_shift is None \
+            else float(reload_max_shift)
+        if self.reload_check < 0:
+            raise ValueError(f"reload_check={reload_check} is negative")
+        if self.reload_max_shift is not None and self.reload_check < 1:
+            raise ValueError("reload_max_shift needs reload_check >= 1")
         # channel attribution (opt-in; None = off, so that a threshold of 0
         # explains every prediction): a persisted prediction with risk >=
         # explain_above is attributed in the same trigger, before
@@ -243,10 +257,84 @@ class FusedServer:
         except Exception as e:  # partial write etc. — retry next trigger
             log.warning("hot reload failed (%s); keeping current model", e)
             return False
-        self.me = MyCNNEngine(model, device=self.device)
+        cand = MyCNNEngine(model, device=self.device)
+        # the file is dealt with either way: a refused one is not vetted
+        # again at every trigger
         self._model_mtime = mtime
+        if self.reload_check > 0 and not self._vet_reload(cand):
+            return False
+        self.me = cand
         log.info("hot-reloaded model from %s", self.model_path)
         return True
+
+    def _vet_reload(self, cand: MyCNNEngine) -> bool:
+        """Score the last reload_check triggers of the live ready slots
+        under the current and the candidate engine, export how far the
+        scores move (gauges reload_*) and say whether the candidate may go
+        live. Kept entries: columns the ring still holds (not NaN under the
+        current model) that lie wholly within the slot's current occupancy.
+        The shift figures are taken over the kept entries whose candidate
+        score is finite; the others are counted in reload_nonfinite. With
+        nothing to compare the swap goes ahead unchecked."""
+        import numpy as _np
+        se, K = self.se, self.reload_check
+        g = self.timer.gauges
+        ready = se.stream_ready()
+        slots = [i for i, p in enumerate(self.pids)
+                 if p is not None and bool(ready[i])]
+        cur = new = None
+        if slots:
+            age = torch.full((se.S, 1), 65.0, device=se.device)
+            col = self._age_column()
+            age[:col.shape[0]] = col
+            try:
+                cur = se.score_history(self.me, slots, k=K, stride=12,
+                                       age=age, apply_sigmoid=True).cpu()
+                new = se.score_history(cand, slots, k=K, stride=12,
+                                       age=age, apply_sigmoid=True).cpu()
+            except ValueError as e:
+                log.warning("reload check unavailable, swapping unchecked: "
+                            "%s", e)
+                cur = None
+        n_kept = 0
+        if cur is not None:
+            ends = se.nproc - 12 * _np.arange(K - 1, -1, -1)
+            since = _np.maximum(se.born[slots], se._origin_nproc)
+            keep = torch.from_numpy(
+                ends[None, :] - se.model_win >= since[:, None]) \
+                & ~torch.isnan(cur)
+            n_kept = int(keep.sum())
+        if n_kept == 0:
+            g["reload_checked_windows"] = 0
+            return True
+        finite = torch.isfinite(new) & keep
+        shift = (new - cur).abs()[finite].double()
+        nonfinite = n_kept - int(finite.sum())
+        smax = float(shift.max()) if shift.numel() else 0.0
+        smean = float(shift.mean()) if shift.numel() else 0.0
+        g.update(reload_checked_windows=n_kept, reload_shift_max=smax,
+                 reload_shift_mean=smean, reload_nonfinite=nonfinite)
+        log.info("reload check: %d windows, shift max %.6f mean %.6f, "
+                 "%d non-finite", n_kept, smax, smean, nonfinite)
+        if self.reload_max_shift is not None and (
+                nonfinite > 0 or smax > self.reload_max_shift):
+            g["reload_rejected_total"] = g.get("reload_rejected_total", 0) + 1
+            log.warning("hot reload of %s refused: shift max %.6f (limit "
+                        "%.6f), %d non-finite; keeping current model",
+                        self.model_path, smax, self.reload_max_shift,
+                        nonfinite)
+            return False
+        return True
+
+    def _age_column(self) -> torch.Tensor:
+        """(slots in use, 1) ages on the device, cached: the column only
+        changes when the slot table does (version counter)."""
+        if getattr(self, "_age_ver", -1) != self._slot_version:
+            self._age_dev = torch.tensor(
+                [[self.ages.get(p) if p is not None else 65.0]
+                 for p in self.pids], device=self.se.device)
+            self._age_ver = self._slot_version
+        return self._age_dev
 
     def _sid(self, pid: str) -> Optional[int]:
         """Host-side mirror of the native key->sid map (poll_samples_sid
@@ -401,11 +489,7 @@ class FusedServer:
         # slot table does (version counter), and the gather overwrites every
         # window element — rebuilding these per trigger cost ~13 ms of
         # Python at 16k live patients (serving_latency_big.json)
-        if getattr(self, "_age_ver", -1) != self._slot_version:
-            self._age_dev = torch.tensor(
-                [[self.ages.get(p) if p is not None else 65.0]
-                 for p in self.pids], device=self.se.device)
-            self._age_ver = self._slot_version
+        age = self._age_column()
         if getattr(self, "_win_buf", None) is None or \
                 self._win_buf.dtype != dtype:
             tl = self.device != "cpu"
@@ -416,7 +500,6 @@ class FusedServer:
         w = self.se.windows(batch=1, stride=12, dtype=dtype,
                             timelast=self.device != "cpu",
                             out=self._win_buf)
-        age = self._age_dev
         probs_all = self.me.forward(w[:n_active].contiguous()
                                     if n_active < self.se.S else w,
                                     age, apply_sigmoid=True)
@@ -716,7 +799,21 @@ def main(argv=None) -> None:
                     help="with --explain-above: what replaces a channel, "
                          "its oldest point in the window (a lead that fell "
                          "off) or 0 (a channel that never arrived)")
+    ap.add_argument("--reload-check", type=int, default=0, metavar="K",
+                    help="with --hot-reload: before a changed checkpoint "
+                         "goes live, score the last K triggers of every "
+                         "live ready stream from the ring under both models "
+                         "and export how far the scores move (0 = off)")
+    ap.add_argument("--reload-max-shift", type=float, default=None,
+                    metavar="D",
+                    help="with --reload-check: keep the current model when "
+                         "the candidate moves any of those scores by more "
+                         "than D or gives a non-finite one")
     args = ap.parse_args(argv)
+    if args.reload_check < 0:
+        ap.error("--reload-check must not be negative")
+    if args.reload_max_shift is not None and args.reload_check < 1:
+        ap.error("--reload-max-shift needs --reload-check")
     if not 0.0 <= args.min_coverage <= 1.0:
         ap.error("--min-coverage must lie in [0, 1]")
     if args.explain_above is not None and args.pipelined:
@@ -751,7 +848,9 @@ def main(argv=None) -> None:
                       snapshot_every=args.snapshot_every,
                       min_coverage=args.min_coverage,
                       explain_above=args.explain_above,
-                      explain_baseline=args.explain_baseline)
+                      explain_baseline=args.explain_baseline,
+                      reload_check=args.reload_check,
+                      reload_max_shift=args.reload_max_shift)
     if args.state_dir:
         os.makedirs(args.state_dir, exist_ok=True)
         srv.state_path = state_file(args.state_dir, rank, world)

@@ -557,6 +557,101 @@ class StreamEngine:
         out = model_engine.forward(v, age, apply_sigmoid=apply_sigmoid)
         return out.reshape(n, C + 1).to(torch.float32)
 
+    # ------------------------------------------------------------ risk history
+    def score_history(self, model_engine, sids=None, k: int = 8,
+                      stride: int = 12, age: Optional[torch.Tensor] = None,
+                      apply_sigmoid: bool = True) -> torch.Tensor:
+        """Scores of the listed streams (all S when ``sids`` is None) at the
+        last ``k`` trigger positions the ring still holds: fp32 ``(n, k)``,
+        one row per listed id, oldest first (the order of ``windows()``'
+        batch axis). Column j is the window ending at ``e_j = nproc -
+        (k-1-j)*stride``, scored as serving scores it (``score_latest`` at
+        ``nproc = e_j``): every window is its own one-step sequence, not a
+        step of an LSTM scan over the batch. A processed point never changes
+        once written, so this is the score a daemon that triggers every
+        ``stride`` grid points produced there.
+
+        With ``lo = max(0, nproc - G, restore floor)``, column j is
+        available iff ``e_j - model_win >= lo``; the unavailable columns are
+        a prefix and come back NaN. Per-occupant validity is not the
+        engine's business: a slot reused after ``reset_streams`` holds zeros
+        below its new occupant's ``born``, and the caller masks the columns
+        with ``e_j - model_win < born[sid]``.
+
+        ``age``: ``(S, 1)`` / ``(S,)`` indexed by stream id, or None; one age
+        serves all columns of a stream. Duplicate ids are harmless, an empty
+        list launches nothing. Runs the fused kernel when
+        ``model_engine.supports_history(C)``, else
+        :meth:`score_history_reference` in fp32. The ring position is passed
+        by value (legal between graph replays, not captured). ValueError: an
+        id outside [0, S), ``k < 1``, ``stride < 1``, no full model window
+        yet, or a newest window that reaches below the restore floor."""
+        assert self._dstate is None, "not inside a device_state block"
+        if not model_engine.supports_history(self.C):
+            return self.score_history_reference(
+                model_engine, sids, k, stride, age, apply_sigmoid)
+        ids, age, jmin = self._history_args(sids, k, stride, age)
+        dids = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+        return model_engine.history_ring(
+            self.proc, self.G, self.nproc, dids, k, stride, jmin, age,
+            apply_sigmoid)
+
+    def _history_args(self, sids, k, stride, age):
+        """Checked arguments of a history call: (int64 ids, age rows of those
+        ids as (n, 1) or None, number of unavailable leading columns)."""
+        assert self.model_win == 120
+        k, stride = int(k), int(stride)
+        if k < 1:
+            raise ValueError(f"k={k}: at least one column")
+        if stride < 1:
+            raise ValueError(f"stride={stride}: at least one grid point")
+        ids = np.arange(self.S, dtype=np.int64) if sids is None \
+            else self._check_sids(sids)
+        if self.nproc < self.model_win:
+            raise ValueError(f"no full model window yet: {self.nproc} of "
+                             f"{self.model_win} grid points")
+        self._check_floor(self.model_win)
+        lo = max(0, self.nproc - self.G, self._proc_floor)
+        room = self.nproc - self.model_win - lo
+        if room < 0:
+            raise ValueError(f"the ring (G={self.G}) is shorter than a "
+                             f"model window of {self.model_win}")
+        jmin = k - min(k, room // stride + 1)
+        if age is not None:
+            age = age.reshape(self.S, 1)[
+                torch.from_numpy(ids).to(age.device)]
+        return ids, age, jmin
+
+    def score_history_reference(self, model_engine, sids=None, k: int = 8,
+                                stride: int = 12,
+                                age: Optional[torch.Tensor] = None,
+                                apply_sigmoid: bool = True,
+                                dtype: torch.dtype = torch.float32
+                                ) -> torch.Tensor:
+        """:meth:`score_history` from existing pieces only: gather the
+        available columns of every stream with ``windows(batch=k - jmin)``
+        (by construction within that method's ring and floor bounds), take
+        the listed rows, score each window as its own one-window sequence
+        with ``model_engine.forward`` and prefix the NaN columns. The
+        fallback for engines the kernel does not cover (CPU, MyCNN2/3) and
+        the kernel's oracle: with ``dtype=torch.bfloat16`` the windows are
+        the time-last bf16 ones the serving path scores."""
+        ids, age, jmin = self._history_args(sids, k, stride, age)
+        n, nav = len(ids), int(k) - jmin
+        out = torch.full((n, int(k)), float("nan"), dtype=torch.float32,
+                         device=self.device)
+        if n == 0:
+            return out
+        w = self.windows(batch=nav, stride=int(stride), dtype=dtype,
+                         timelast=dtype == torch.bfloat16)
+        x = w[torch.from_numpy(ids).to(w.device)]        # (n, nav, ...)
+        x = x.reshape(n * nav, 1, *x.shape[-2:])
+        if age is not None:
+            age = age.to(torch.float32).repeat_interleave(nav, dim=0)
+        y = model_engine.forward(x, age, apply_sigmoid=apply_sigmoid)
+        out[:, jmin:] = y.reshape(n, nav).to(torch.float32)
+        return out
+
     @property
     def ready(self) -> bool:
         """A full model window exists (>= 600 s + 180 s of data SINCE THE

@@ -25,7 +25,14 @@ STREAM_STATES = ("active", "admitted_total", "evicted_total",
                  "withheld_total", "coverage_mean", "coverage_unavailable",
                  # channel attribution (serve --explain-above): predictions
                  # that were attributed since start
-                 "explained_total")
+                 "explained_total",
+                 # hot-reload vetting (serve --reload-check): past windows
+                 # compared at the last changed checkpoint, how far the
+                 # candidate moved their scores, its non-finite scores, and
+                 # candidates refused since start (--reload-max-shift)
+                 "reload_checked_windows", "reload_shift_max",
+                 "reload_shift_mean", "reload_nonfinite",
+                 "reload_rejected_total")
 
 
 class StageTimer:

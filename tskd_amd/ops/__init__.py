@@ -212,6 +212,47 @@ class MyCNNEngine:
             self.variant, hip.stream_ptr()), "tskd_serve_tail_occlude_fwd")
         return out
 
+    def supports_history(self, n_channels: int) -> bool:
+        """True when :meth:`history_ring` applies: the coverage of
+        :meth:`score_ring`."""
+        return self.supports_fused_tail(n_channels)
+
+    def history_ring(self, proc: torch.Tensor, G: int, end: int, sids,
+                     k: int, stride: int, jmin: int,
+                     age: Optional[torch.Tensor] = None,
+                     apply_sigmoid: bool = False) -> torch.Tensor:
+        """Scores of the listed streams at ``k`` window positions straight
+        from a StreamEngine's (S, C, G) fp32 ``proc`` ring, in ONE kernel:
+        (n, k) fp32, column j the score of the window ending at ``end -
+        (k-1-j)*stride`` as :meth:`score_ring` gives it at that end (every
+        window its own one-step sequence), oldest first. Columns below
+        ``jmin`` are NaN and nothing of them is read; column ``jmin`` must
+        neither start before grid point 0 nor reach slots the ring has
+        already overwritten (``end - G``), else the launcher refuses with
+        code -5. ``sids``: int32 device tensor of n stream ids (rows follow
+        it, duplicates are harmless, an id outside [0, S) is skipped and its
+        row left unwritten); ``age``: (n,) / (n, 1) per listed stream, one
+        age for all of its columns, or None. The ring position is passed by
+        value: legal between graph replays, not captured. Raises for
+        variants the kernel does not cover."""
+        assert proc.dim() == 3 and proc.dtype == torch.float32 \
+            and proc.is_contiguous() and proc.shape[2] == G
+        assert sids.dtype == torch.int32 and sids.dim() == 1 \
+            and sids.is_contiguous() and sids.device == proc.device
+        s, c, n = proc.shape[0], proc.shape[1], sids.numel()
+        out = torch.empty(n, int(k), dtype=torch.float32, device=proc.device)
+        if n == 0:
+            return out
+        age_ptr, age = _age_ptr(
+            None if age is None else age.reshape(n, 1), n, 1)
+        hip.check(hip.load(hip.MYCNN).tskd_serve_tail_history_fwd(
+            hip.ptr(proc), s, c, int(G), int(end), hip.ptr(sids), n, age_ptr,
+            int(k), int(stride), int(jmin), hip.ptr(out),
+            hip.ptr(self.wpack), hip.ptr(self.bfrag), self.age_eps,
+            int(apply_sigmoid), self.variant, hip.stream_ptr()),
+            "tskd_serve_tail_history_fwd")
+        return out
+
     def forward(self, x: torch.Tensor, age: Optional[torch.Tensor] = None,
                 apply_sigmoid: bool = False) -> torch.Tensor:
         """x: (N, C, 120) single sequence, or (S, N, C, 120).

@@ -43,6 +43,9 @@
 //      variants of a listed stream's window (one channel held flat or zeroed
 //      per variant), the ring window read once per stream.
 //
+//   5. serve_tail_history_kernel: risk history — kernel 3 on K past window
+//      positions of a listed stream that the ring still holds.
+//
 //   debug_mfma_kernel: one 16x16x32 bf16 MFMA tile, the fragment-map ground
 //   truth for the tests.
 //
@@ -1096,6 +1099,123 @@ __global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_occlude_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Kernel 5 (risk history): scores of listed streams at K past window
+// positions straight from the ring. Column j is the window ending at
+// e_j = end - (K-1-j)*stride (oldest first, the order of the window gather's
+// batch axis), scored as serve_tail_kernel scores it at end = e_j: its own
+// one-step sequence. Columns j < jmin reach below what the ring still holds;
+// they get a quiet NaN and none of their addresses is formed. out is (n, K).
+//
+// Schedule: kernel 4's flat loop, the wave's pair of images being two
+// consecutive columns of one stream: one wave per (listed stream, round)
+// item, (K + 1) / 2 rounds per stream. Each image has its own ring read
+// (uniform start, one compare-and-subtract wrap); at stride 12 two
+// neighbouring windows share 108 of their 120 points and a workgroup's 4
+// waves mostly take rounds of one stream, so L1/L2 serve the repeats. A
+// round with one column below jmin stages the zero image for it
+// (ring_load(live = false)) and skips its tail; a round with both below
+// jmin only writes the NaNs. Odd K's last round has the newest column alone:
+// its absent partner is a zero image without a tail, too.
+// ---------------------------------------------------------------------------
+template <class G>
+__global__ __launch_bounds__(WG_THREADS, 4) void serve_tail_history_kernel(
+    const float* __restrict__ proc,   // (S, CIN, ring) fp32 processed ring
+    const int* __restrict__ sids,     // (n) stream ids
+    const float* __restrict__ age,    // (n) or nullptr
+    float* __restrict__ out,          // (n, K)
+    const float* __restrict__ wpack,
+    const unsigned short* __restrict__ bfrag,  // [KSTEPS][64][8] bf16 bits
+    int S, int n, int ring, long end, int K, int stride, int jmin,
+    float age_eps, int apply_sigmoid)
+{
+    using T = Tail<G>;
+    __shared__ float lds_w[G::NW];
+    __shared__ unsigned int lds_xt[WG_WAVES][2][T::XTD];
+    __shared__ float lds_c1[WG_WAVES][2][4 * G::C1];
+
+    for (int i = threadIdx.x; i < G::NW; i += WG_THREADS) lds_w[i] = wpack[i];
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+    const int lane = threadIdx.x % WAVE;
+    const float* b1 = lds_w + G::OB1;
+    unsigned int* xta = lds_xt[wave][0];
+    unsigned int* xtb = lds_xt[wave][1];
+    float* c1a = lds_c1[wave][0];
+    float* c1b = lds_c1[wave][1];
+    float* p1w = (float*)xta;
+    float* c2w = p1w + 4 * G::P1;
+    float* fw = c2w + G::C2;
+
+    T tw;
+    tw.load(wpack, bfrag, lane);
+
+    for (int i = G::XTN / 2 + lane; i < T::XTD; i += WAVE)
+        xta[i] = xtb[i] = 0u;
+
+    // The launcher guarantees L <= e_jmin, (K-1)*stride < 2^30 and ring <=
+    // 2^29: the newest window's start slot, and per column the distance back
+    // from it, are 32-bit.
+    const int start_new = (int)((end - G::L) % ring);
+    const float qnan = __builtin_nanf("");
+
+    // One item = one round of one listed stream = columns ja, ja + 1.
+    const int NR = (K + 1) / 2;
+    for (long item = blockIdx.x * WG_WAVES + wave; item < (long)n * NR;
+         item += (long)gridDim.x * WG_WAVES) {
+        const long i = item / NR;
+        const int ja = (int)(item % NR) * 2, jb = ja + 1;
+        const bool hasb = jb < K;
+        const bool livea = ja >= jmin, liveb = hasb && jb >= jmin;
+        // uniform: say so, so the ring row base is scalar
+        const long s = __builtin_amdgcn_readfirstlane(sids[i]);
+        if (s < 0 || s >= S) continue;    // the host refuses these ids
+        // jmin <= K - 1 and the unavailable columns are a prefix: a round
+        // without a live column has both, and a live a has a live b or none
+        if (!livea && !liveb) {
+            if (lane == 0) out[i * K + ja] = out[i * K + jb] = qnan;
+            continue;
+        }
+        // slot of a live column's oldest point; 0 for one that is not live
+        // (nothing is read through its offsets)
+        auto start_of = [&](int j, bool live) {
+            if (!live) return 0;
+            const int back = (int)((unsigned int)((K - 1 - j) * stride)
+                                   % (unsigned int)ring);
+            const int st = start_new - back;
+            return st < 0 ? st + ring : st;
+        };
+        // image a is staged completely before image b's offsets are formed:
+        // with both reads issued first the 40 loads are hoisted together
+        // and MyCNN5 spills 3 VGPRs at the 128 of these launch bounds
+        auto stage = [&](unsigned int* xt, int j, bool live) {
+            unsigned int goff[T::NT], pk[T::NT][T::CD];
+            T::ring_offsets(start_of(j, live), ring, lane, goff);
+            T::ring_load(proc, s, ring, goff, lane, live, pk);
+            T::image_store(xt, lane, pk);
+        };
+        stage(xta, ja, livea);
+        stage(xtb, jb, liveb);
+        wave_sync();
+
+        tw.conv1_pair(xta, xtb, c1a, c1b, b1, lane);
+        wave_sync();  // both images are dead from here: scratch may land
+        if (livea) {
+            conv_tail<G, true>(lane, lds_w, c1a, p1w, c2w, fw, 0);
+            tw.lstm_step(fw, lane, age, i, out, i * K + ja, age_eps,
+                         apply_sigmoid);
+        } else if (lane == 0) {
+            out[i * K + ja] = qnan;
+        }
+        if (liveb) {
+            conv_tail<G, true>(lane, lds_w, c1b, p1w, c2w, fw, 0);
+            tw.lstm_step(fw, lane, age, i, out, i * K + jb, age_eps,
+                         apply_sigmoid);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Debug: one 16x16x32 bf16 MFMA tile (fragment-map ground truth for tests)
 // ---------------------------------------------------------------------------
 __global__ void debug_mfma_kernel(const unsigned short* __restrict__ A,
@@ -1228,11 +1348,62 @@ int launch_serve_tail_occlude(const float* proc, int S, int C, int ring,
     }
 }
 
+// Risk history: serve_tail's coverage and codes. -5 as well for a column
+// geometry the kernel's 32-bit slot arithmetic does not take and for a jmin
+// whose column would read an overwritten or negative ring position.
+template <class G>
+int launch_serve_tail_history(const float* proc, int S, int C, int ring,
+                              long end, const int* sids, int n,
+                              const float* age, int K, int stride, int jmin,
+                              float* out, const float* wpack,
+                              const void* bfrag, float age_eps,
+                              int apply_sigmoid, hipStream_t stream) {
+    if constexpr (G::CIN % 2 != 0) {
+        return SERVE_TAIL_UNSUPPORTED;
+    } else {
+        if (C != G::CIN) return SERVE_TAIL_UNSUPPORTED;
+        if (ring < G::L || ring > (1 << 29)) return -5;
+        if (K < 1 || stride < 1 || (long)(K - 1) * stride >= (1L << 30))
+            return -5;
+        if (jmin < 0 || jmin > K - 1) return -5;
+        const long lo = end - ring > 0 ? end - ring : 0;
+        if (end - (long)(K - 1 - jmin) * stride - G::L < lo) return -5;
+        if (!bfrag) return -2;
+        if (n <= 0) return 0;
+        // one wave per (stream, round of two columns)
+        const long items = (long)n * ((K + 1) / 2);
+        const int g1 = (int)((items < 4 * 8192L ? items : 4 * 8192L)
+                             + WG_WAVES - 1) / WG_WAVES;
+        hipLaunchKernelGGL((serve_tail_history_kernel<G>), dim3(g1),
+                           dim3(WG_THREADS), 0, stream, proc, sids, age, out,
+                           wpack, (const unsigned short*)bfrag, S, n, ring,
+                           end, K, stride, jmin, age_eps, apply_sigmoid);
+        return (int)hipGetLastError();
+    }
+}
+
 }  // namespace
 
 extern "C" {
 
 // variant (everywhere below): 0 = MyCNN5, 1 = MyCNN2/3, 2 = MyCNN4
+
+// Scores (n, K) of the listed streams at K window positions of the (S, C, G)
+// fp32 ring: column j ends at end - (K-1-j)*stride; columns below jmin are
+// NaN and read nothing; age is (n) or null.
+int tskd_serve_tail_history_fwd(const float* proc, int S, int C, int G,
+                                long end, const int* sids, int n,
+                                const float* age, int K, int stride, int jmin,
+                                float* out, const float* wpack,
+                                const void* bfrag, float age_eps,
+                                int apply_sigmoid, int variant,
+                                void* stream) {
+    return dispatch_variant(variant, [&](auto g) {
+        return launch_serve_tail_history<typename decltype(g)::type>(
+            proc, S, C, G, end, sids, n, age, K, stride, jmin, out, wpack,
+            bfrag, age_eps, apply_sigmoid, (hipStream_t)stream);
+    });
+}
 
 // Occlusion scores (n, C + 1) of the listed streams' latest windows ending at
 // `end` in the (S, C, G) fp32 ring; baseline 0 = hold, 1 = zero; age is (n)

@@ -27,6 +27,8 @@ SIGNATURES = {
         "tskd_serve_tail_fwd": [P, I, I, I, L, P, I, P, P, P, P, F, I, I, P],
         "tskd_serve_tail_occlude_fwd": [P, I, I, I, L, P, I, P, I, P, P, P, F,
                                         I, I, P],
+        "tskd_serve_tail_history_fwd": [P, I, I, I, L, P, I, P, I, I, I, P, P,
+                                        P, F, I, I, P],
         "tskd_conv_fwd": [P, I, I, P, P, P, I, I, P],
         "tskd_lstm_head_fwd": [P, P, P, P, I, I, F, I, I, P],
         "tskd_debug_mfma16x16x32": [P, P, P, P],
