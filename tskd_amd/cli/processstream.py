@@ -23,7 +23,7 @@ from typing import Dict, Optional
 import torch
 
 from tskd_amd.bus import Bus, Consumer, Producer
-from tskd_amd.config import get_global_config
+from tskd_amd.config import get_global_config, resolve_valid_ranges
 from tskd_amd.engine import StreamEngine
 
 log = logging.getLogger("processStream")
@@ -33,15 +33,21 @@ class ProcessStream:
     def __init__(self, bus: Bus, cfg, max_streams: int = 64,
                  device: str = "cpu", starting: str = "latest",
                  watermark_s: float = 10.0, out_topic: str = "call-stream",
-                 evict_idle_s: float = 0.0):
+                 evict_idle_s: float = 0.0, valid_range=None):
         self.bus = bus
         # stream lifecycle (opt-in; 0 = off): see FusedServer. When on, the
         # native slot table is the one allocator (poll_samples_sid).
         self.evict_idle_s = float(evict_idle_s)
         self.cfg = cfg
         self.out_topic = out_topic
+        # signal-quality gate (opt-in; None = off): see FusedServer.
+        # engine.rejected() holds the per-(stream, channel) counts; their
+        # growth since start, by channel name, is in rejected_samples.
         self.engine = StreamEngine(max_streams, cfg.n_channels,
-                                   ring_grid=4096, device=device)
+                                   ring_grid=4096, device=device,
+                                   valid_range=valid_range)
+        self.rejected_samples: Dict[str, int] = {}
+        self._rej_prev = None
         self.consumer = Consumer(bus, starting=starting)
         topics = [cfg.topic_for_channel(c) for c in cfg.channel_names]
         for t in topics:
@@ -86,7 +92,10 @@ class ProcessStream:
             if self.pid_index.get(key) == sid:
                 del self.pid_index[key]
         if pairs:
-            self.engine.reset_streams([sid for _k, sid in pairs])
+            sids = [sid for _k, sid in pairs]
+            self.engine.reset_streams(sids)     # zeroes their rej rows too
+            if self._rej_prev is not None:
+                self._rej_prev[sids] = 0
 
     def _drain_lifecycle(self):
         """Drain through the native slot table (the one allocator). Event
@@ -122,6 +131,13 @@ class ProcessStream:
                 self.engine._clear_ahead(new_head)
                 self.engine.head = new_head
                 self.engine._refill()
+        if self.engine.rej is not None:
+            cur = self.engine.rej.cpu().numpy().copy()  # CPU: not a view
+            delta = cur if self._rej_prev is None else cur - self._rej_prev
+            self._rej_prev = cur
+            for c, name in enumerate(self.cfg.channel_names):
+                self.rejected_samples[name] = \
+                    self.rejected_samples.get(name, 0) + int(delta[:, c].sum())
         np_new = self.engine.nproc - nproc_before
         if np_new <= 0:
             return 0
@@ -180,16 +196,29 @@ def main(argv=None) -> None:
                     help="retention: reclaim bus storage behind THIS "
                          "consumer's position after each trigger (only safe "
                          "when no other consumer needs the raw topics)")
+    ap.add_argument("--valid-range", action="append", default=None,
+                    metavar="SPEC",
+                    help="signal-quality gate (repeatable): NAME=LO:HI keeps "
+                         "only samples of channel NAME inside [LO, HI] "
+                         "(either side empty = open), 'numerics' selects "
+                         "the preset that drops the monitors' no-reading "
+                         "code 0. Overrides the config's VALID_RANGES (off "
+                         "unless either is given)")
     args = ap.parse_args(argv)
     if args.signal_list:
         cfg.channel_names = args.signal_list
+    try:
+        valid_range = resolve_valid_ranges(cfg, args.valid_range)
+    except ValueError as e:
+        ap.error(str(e))
 
     bus = Bus(args.bus_dir)
     ps = ProcessStream(bus, cfg, max_streams=args.max_streams,
                        device=args.device, starting=args.starting,
                        watermark_s=cfg.watermark_s,
                        out_topic=args.model_call_topic,
-                       evict_idle_s=args.evict_idle_s)
+                       evict_idle_s=args.evict_idle_s,
+                       valid_range=valid_range)
     trigger_period = cfg.preprocess_trigger_s / args.speed
     stop = []
     signal.signal(signal.SIGTERM, lambda *a: stop.append(1))
@@ -211,6 +240,7 @@ def main(argv=None) -> None:
         with timer:
             out = ps.trigger()
         timer.add_items(out)
+        timer.rejected_samples = ps.rejected_samples
         if args.offsets_file:
             save_offsets(args.offsets_file, ps.consumer.positions())
         if args.trim_consumed:

@@ -32,7 +32,8 @@ from typing import Dict, Optional
 import torch
 
 from tskd_amd.bus import Bus, Consumer, Producer
-from tskd_amd.config import get_global_config
+from tskd_amd.config import (engine_valid_range, get_global_config,
+                             resolve_valid_ranges)
 from tskd_amd.engine import EngineSnapshot, StreamEngine
 from tskd_amd.metrics import StageTimer
 from tskd_amd.models import build_model
@@ -57,7 +58,8 @@ class FusedServer:
                  min_coverage: float = 0.0,
                  explain_above: Optional[float] = None,
                  explain_baseline: str = "hold", reload_check: int = 0,
-                 reload_max_shift: Optional[float] = None):
+                 reload_max_shift: Optional[float] = None,
+                 valid_range=None):
         self.cfg = cfg
         # hot-reload vetting (opt-in; 0 = off): before a changed checkpoint
         # goes live, the last reload_check triggers of the live ready slots
@@ -109,8 +111,26 @@ class FusedServer:
                               device=device)
         # ring channel space = the MODEL's wire space (config may name fewer
         # channels; the rest stay zero, like the reference's fixed (1,10,120))
-        self.se = StreamEngine(max_streams, max(cfg.n_channels, self.me.cin),
-                               ring_grid=ring_grid, device=device)
+        # signal-quality gate (opt-in; None = off): per config channel a
+        # closed plausibility interval (lo, hi); a sample outside it that is
+        # not NaN is rejected at ingest and the engine counts it (se.rej).
+        # Each trigger copies the counter to the host once and feeds the
+        # per-channel counters, the gauges and the responses' "rejected"
+        # from the delta against the previous copy.
+        n_ring = max(cfg.n_channels, self.me.cin)
+        if valid_range is not None and len(valid_range) != cfg.n_channels:
+            raise ValueError(f"valid_range has {len(valid_range)} entries "
+                             f"for {cfg.n_channels} config channels")
+        self.se = StreamEngine(max_streams, n_ring,
+                               ring_grid=ring_grid, device=device,
+                               valid_range=engine_valid_range(valid_range,
+                                                              n_ring))
+        self._gated = self.se.rej is not None
+        if self._gated:
+            import numpy as _np
+            self._rej_prev = _np.zeros((max_streams, n_ring), _np.int64)
+            # per slot: rejected since the slot's last published prediction
+            self._rej_since = _np.zeros(max_streams, _np.int64)
         self.consumer = Consumer(bus, starting=starting)
         topics = [cfg.topic_for_channel(c) for c in cfg.channel_names]
         for t in topics:
@@ -365,7 +385,11 @@ class FusedServer:
             if sid < len(self.pids) and self.pids[sid] == key:
                 self.pids[sid] = None
         self._slot_version += 1
-        self.se.reset_streams([sid for _k, sid in pairs])
+        sids = [sid for _k, sid in pairs]
+        self.se.reset_streams(sids)     # zeroes the slots' rej rows too
+        if self._gated:
+            self._rej_prev[sids] = 0
+            self._rej_since[sids] = 0
 
     def _admit(self, new_keys, sa, ta) -> None:
         """Admit the trigger's new patients: each one's warm-up counts from
@@ -381,6 +405,28 @@ class FusedServer:
         t_first[~_np.isfinite(t_first)] = 0.0   # no live sample: from now
         self.se.admit(sids, at=(t_first // self.se.bucket_s).astype(
             _np.int64))
+
+    def _count_rejected(self) -> None:
+        """One device-to-host copy of the engine's rejected counter; its
+        delta against the previous copy goes to the per-channel counters
+        (tskd_rejected_samples_total), the gauges and the per-slot tally
+        that the next published prediction of the slot reports."""
+        n = len(self.pids)
+        nc = self.cfg.n_channels
+        cur = self.se.rej[:n].cpu().numpy()
+        delta = cur - self._rej_prev[:n]
+        self._rej_prev[:n] = cur
+        self._rej_since[:n] += delta[:, :nc].sum(axis=1)
+        per = self.timer.rejected_samples
+        for c, name in enumerate(self.cfg.channel_names):
+            per[name] = per.get(name, 0) + int(delta[:, c].sum())
+        g = self.timer.gauges
+        total = g.get("rejected_samples_total", 0) + int(delta[:, :nc].sum())
+        g["rejected_samples_total"] = total
+        if not self._lifecycle:
+            # with --evict-idle-s this state counts the samples of patients
+            # turned away at a full slot table (_update_gauges)
+            g["rejected_total"] = total
 
     def _update_gauges(self) -> None:
         c = self.consumer
@@ -433,6 +479,8 @@ class FusedServer:
                     advance_to=advance)
             else:
                 self.se.advance_watermark(advance)
+            if self._gated and self.pids:
+                self._count_rejected()
             t0 = self._stamp("ingest", t0)
             np_new = self.se.nproc - nproc_before
             if self.emit_processed and np_new > 0 and self.pids:
@@ -514,12 +562,14 @@ class FusedServer:
         imputed = self._imputed_inputs(n_active) \
             if self.min_coverage > 0.0 else None
         t0 = self._stamp("model", t0)
+        rejected = self._rej_since[:n_active].copy() if self._gated else None
         if self.pipelined:
             # defer the device sync: persist at the next trigger start,
             # after the bus poll has overlapped this trigger's GPU work
-            self._pending = (probs, t_us, list(self.pids), mask, imputed)
+            self._pending = (probs, t_us, list(self.pids), mask, imputed,
+                             rejected)
         else:
-            self._persist(probs, t_us, self.pids, mask, imputed)
+            self._persist(probs, t_us, self.pids, mask, imputed, rejected)
         self._stamp("persist", t0)
         n_scored = n_active if mask is None else sum(mask)
         self.timer.add_items(n_scored)
@@ -583,7 +633,7 @@ class FusedServer:
                 for r, j in enumerate(pick)}
 
     def _persist(self, probs, t_us: int, pids, mask=None,
-                 imputed=None) -> None:
+                 imputed=None, rejected=None) -> None:
         q = None
         slots = range(len(pids))
         if imputed is not None:
@@ -608,14 +658,23 @@ class FusedServer:
             local = probs.reshape(-1)[:n].cpu()
             self.store.insert_batch(pids, [t_us] * n, local.tolist())
             self.n_predictions += n
+        rej = None
+        if rejected is not None:
+            # what each published slot's tally held when it was scored; the
+            # tally keeps what was rejected since (a pipelined persist runs
+            # one trigger later) and restarts from there
+            sl = list(slots)
+            rej = rejected[sl]
+            self._rej_since[sl] = (self._rej_since[sl] - rej).clip(min=0)
         if self.producer and self.response_topic:
             vals = probs.reshape(-1)[:n].cpu()
             for i, pid in enumerate(pids):
                 cov = "" if q is None else f', "coverage": {q[i]:.4f}'
+                rj = "" if rej is None else f', "rejected": {int(rej[i])}'
                 self.producer.produce(
                     self.response_topic, pid,
                     f'{{"t_us": {t_us}, "risk": {float(vals[i]):.6f}{cov}'
-                    f'{attr.get(i, "")}}}')
+                    f'{rj}{attr.get(i, "")}}}')
 
     def flush(self) -> None:
         """Persist the deferred trigger (pipelined mode; call on shutdown
@@ -809,7 +868,21 @@ def main(argv=None) -> None:
                     help="with --reload-check: keep the current model when "
                          "the candidate moves any of those scores by more "
                          "than D or gives a non-finite one")
+    ap.add_argument("--valid-range", action="append", default=None,
+                    metavar="SPEC",
+                    help="signal-quality gate (repeatable): NAME=LO:HI keeps "
+                         "only samples of channel NAME inside [LO, HI] "
+                         "(either side empty = open), 'numerics' selects "
+                         "the preset that drops the monitors' no-reading "
+                         "code 0; rejected samples count as missing and are "
+                         "exported as tskd_rejected_samples_total. "
+                         "Overrides the config's VALID_RANGES (off unless "
+                         "either is given)")
     args = ap.parse_args(argv)
+    try:
+        valid_range = resolve_valid_ranges(cfg, args.valid_range)
+    except ValueError as e:
+        ap.error(str(e))
     if args.reload_check < 0:
         ap.error("--reload-check must not be negative")
     if args.reload_max_shift is not None and args.reload_check < 1:
@@ -850,7 +923,8 @@ def main(argv=None) -> None:
                       explain_above=args.explain_above,
                       explain_baseline=args.explain_baseline,
                       reload_check=args.reload_check,
-                      reload_max_shift=args.reload_max_shift)
+                      reload_max_shift=args.reload_max_shift,
+                      valid_range=valid_range)
     if args.state_dir:
         os.makedirs(args.state_dir, exist_ok=True)
         srv.state_path = state_file(args.state_dir, rank, world)

@@ -14,7 +14,7 @@ import configparser
 import os
 import sys
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import List, Optional, Sequence, Tuple
 
 # Wire/tensor channel order — the index order IS the channel order on the wire
 # and in the (N, C, 120) model tensor (reference config.cfg:23 CHANNEL_NAMES).
@@ -27,6 +27,88 @@ DEFAULT_PATIENT_RECORDS: List[str] = [
     "p000194-2112-05-23-14-34n",
     "p044083-2112-05-04-19-50n",
 ]
+
+# Signal-quality gate presets (docs/PARITY.md divergence 15): closed
+# plausibility intervals by channel name; a channel not named is open on both
+# sides. ``numerics`` is deliberately loose: it removes the monitor's
+# no-reading code (0) and the physically impossible, nothing else. CVP, ST V
+# and PVC Rate per Minute stay open: 0 and negative values are legitimate
+# there.
+VALID_RANGE_PRESETS = {
+    "numerics": {
+        "HR": (1.0, 350.0), "PULSE": (1.0, 350.0), "RESP": (1.0, 150.0),
+        "SpO2": (1.0, 100.0), "NBP Sys": (1.0, 400.0),
+        "NBP Dias": (1.0, 400.0), "NBP Mean": (1.0, 400.0),
+    },
+}
+
+Range = Tuple[Optional[float], Optional[float]]
+
+
+def parse_valid_ranges(specs: Sequence[str],
+                       channel_names: Sequence[str]) -> List[Range]:
+    """Per-channel ``(lo, hi)`` plausibility bounds, in ``channel_names``
+    order, from a list of specs; None = open on that side, and a channel no
+    spec names is ``(None, None)``. A spec is a preset name (``numerics``;
+    its channels that ``channel_names`` lacks are skipped) or ``NAME=LO:HI``
+    with either side empty for open: ``HR=1:350``, ``SpO2=1:``, ``ST V=:``.
+    Later specs override earlier ones. ValueError: an unknown channel or
+    preset name, a malformed spec, a bound that is no number or NaN, or
+    lo > hi."""
+    names = list(channel_names)
+    out: List[Range] = [(None, None)] * len(names)
+    for spec in specs:
+        spec = spec.strip()
+        if spec in VALID_RANGE_PRESETS:
+            for name, rng in VALID_RANGE_PRESETS[spec].items():
+                if name in names:
+                    out[names.index(name)] = rng
+            continue
+        name, eq, rng = spec.partition("=")
+        name = name.strip()
+        if not eq or rng.count(":") != 1:
+            raise ValueError(f"valid range {spec!r}: expected NAME=LO:HI or "
+                             f"one of {sorted(VALID_RANGE_PRESETS)}")
+        if name not in names:
+            raise ValueError(f"valid range {spec!r}: unknown channel "
+                             f"{name!r} (known: {names})")
+        bounds = []
+        for side in rng.split(":"):
+            side = side.strip()
+            try:
+                bounds.append(float(side) if side else None)
+            except ValueError:
+                raise ValueError(f"valid range {spec!r}: {side!r} is not a "
+                                 f"number") from None
+        lo, hi = bounds
+        if any(b is not None and b != b for b in bounds):
+            raise ValueError(f"valid range {spec!r}: NaN bound")
+        if lo is not None and hi is not None and lo > hi:
+            raise ValueError(f"valid range {spec!r}: lo > hi")
+        out[names.index(name)] = (lo, hi)
+    return out
+
+
+def resolve_valid_ranges(cfg: "GlobalConfig",
+                         flag_specs: Optional[Sequence[str]] = None
+                         ) -> Optional[List[Range]]:
+    """The gate's bounds for ``cfg.channel_names``: from the command line's
+    specs when any were given (they override the config key as a whole), else
+    from the config's VALID_RANGES, else None (no gate)."""
+    specs = list(flag_specs) if flag_specs else list(cfg.valid_ranges)
+    if not specs:
+        return None
+    return parse_valid_ranges(specs, cfg.channel_names)
+
+
+def engine_valid_range(ranges: Optional[Sequence[Range]],
+                       n_channels: int) -> Optional[List[Range]]:
+    """``ranges`` (by config channel) padded with open intervals to an
+    engine's ``n_channels`` wire channels; None stays None."""
+    if ranges is None:
+        return None
+    ranges = list(ranges)
+    return ranges + [(None, None)] * (n_channels - len(ranges))
 
 
 @dataclass
@@ -62,6 +144,10 @@ class GlobalConfig:
     predict_window_s: float = 600.0
     predict_slide_s: float = 60.0
     watermark_s: float = 10.0
+
+    # Signal-quality gate specs ([SETTINGS] VALID_RANGES, optional; the
+    # reference's config.cfg has no such key): see parse_valid_ranges.
+    valid_ranges: List[str] = field(default_factory=list)
 
     # Bus defaults (reference utils.py:417-428): acks=all, retries=5,
     # startingOffsets=latest.
@@ -131,6 +217,9 @@ def get_global_config(path: Optional[str] = None) -> GlobalConfig:
         cfg.window_size = int(s.get("WINDOWSIZE", cfg.window_size))
         cfg.record_overlap = float(s.get("RECORDOVERLAP", cfg.record_overlap))
         cfg.batch_size = int(s.get("BATCHSIZE", cfg.batch_size))
+        if "VALID_RANGES" in s:
+            cfg.valid_ranges = _split_csv(s["VALID_RANGES"])
+            parse_valid_ranges(cfg.valid_ranges, cfg.channel_names)  # vet
 
     if parser.has_section("BUS"):
         b = parser["BUS"]

@@ -34,6 +34,31 @@ from tskd_amd.ops import hip
 GPU_MAX_WIN_BUCKETS = 64
 
 
+def check_valid_range(valid_range, n_channels: int) -> np.ndarray:
+    """``valid_range`` — a length-C sequence of ``(lo, hi)``, None meaning
+    open on that side — as fp32 ``(C, 2)`` bounds with ±inf for the open
+    sides. ValueError: a wrong length, a NaN bound, or lo > hi."""
+    rows = list(valid_range)
+    if len(rows) != n_channels:
+        raise ValueError(f"valid_range has {len(rows)} entries for "
+                         f"{n_channels} channels")
+    out = np.empty((n_channels, 2), dtype=np.float32)
+    for c, row in enumerate(rows):
+        try:
+            lo, hi = row
+        except (TypeError, ValueError):
+            raise ValueError(f"valid_range[{c}]={row!r} is not a (lo, hi) "
+                             f"pair") from None
+        lo = -np.inf if lo is None else np.float32(lo)
+        hi = np.inf if hi is None else np.float32(hi)
+        if np.isnan(lo) or np.isnan(hi):
+            raise ValueError(f"valid_range[{c}] has a NaN bound")
+        if lo > hi:
+            raise ValueError(f"valid_range[{c}]: lo={lo} > hi={hi}")
+        out[c] = lo, hi
+    return out
+
+
 class StreamEngine:
     """Event-time sliding-window engine over S streams x C channels.
 
@@ -46,7 +71,8 @@ class StreamEngine:
     def __init__(self, n_streams: int, n_channels: int = 10,
                  ring_grid: int = 4096, fs: float = 125.0,
                  bucket_s: float = W.BUCKET_S, win_buckets: int = W.WIN_BUCKETS,
-                 model_win: int = W.MODEL_WIN, device: str = "cpu"):
+                 model_win: int = W.MODEL_WIN, device: str = "cpu",
+                 valid_range=None):
         self.S, self.C, self.G = n_streams, n_channels, ring_grid
         self.fs = fs
         self.bucket_s = bucket_s
@@ -98,6 +124,17 @@ class StreamEngine:
         # present (their state is unknown)
         self._bucket_floor = 0
         self._snap_dev = self._snap_host = None  # reused staging buffers
+        # signal-quality gate (opt-in, docs/PARITY.md divergence 15): per
+        # wire channel a closed interval [lo, hi]; a sample outside it that
+        # is not NaN is rejected at ingest (neither summed nor counted) and
+        # adds 1 to the cumulative (S, C) int64 counter ``rej``. None: no
+        # gate, nothing allocated, every launch the ungated one.
+        self.bounds = self.rej = None
+        if valid_range is not None:
+            self.bounds = torch.from_numpy(
+                check_valid_range(valid_range, self.C)).to(dev)
+            self.rej = torch.zeros(self.S, self.C, dtype=torch.int64,
+                                   device=dev)
         if self._gpu:
             hip.load(hip.PREPROC)  # fail here, not at the first launch
 
@@ -127,13 +164,19 @@ class StreamEngine:
     def _launch_ingest(self, raw: torch.Tensor, chan_map) -> None:
         """Dense bucket ingest of contiguous fp32/bf16 ``raw`` at head (the
         kernel takes the device state block's head when one is set)."""
-        hip.check(hip.load(hip.PREPROC).tskd_preproc_ingest_dense(
-            hip.ptr(raw), int(raw.dtype == torch.bfloat16),
-            hip.ptr(self.bsum), hip.ptr(self.bcnt),
-            hip.ptr(self._chan_map_tensor(chan_map)), self.S, raw.shape[1],
-            self.C, raw.shape[2], self.G, self.bucket_len, self.head,
-            self._dstate_ptr(), self._bst, hip.stream_ptr()),
-            "tskd_preproc_ingest_dense")
+        lib = hip.load(hip.PREPROC)
+        args = (hip.ptr(raw), int(raw.dtype == torch.bfloat16),
+                hip.ptr(self.bsum), hip.ptr(self.bcnt),
+                hip.ptr(self._chan_map_tensor(chan_map)), self.S,
+                raw.shape[1], self.C, raw.shape[2], self.G, self.bucket_len,
+                self.head, self._dstate_ptr(), self._bst)
+        if self.bounds is None:
+            hip.check(lib.tskd_preproc_ingest_dense(*args, hip.stream_ptr()),
+                      "tskd_preproc_ingest_dense")
+        else:
+            hip.check(lib.tskd_preproc_ingest_dense_gated(
+                *args, hip.ptr(self.bounds), hip.ptr(self.rej),
+                hip.stream_ptr()), "tskd_preproc_ingest_dense_gated")
 
     def _launch_fill(self, phead: int, np_new: int) -> None:
         """Window fill of ``np_new`` grid points from ``phead`` (or from the
@@ -177,9 +220,18 @@ class StreamEngine:
             self._clear_stale_channels(chan_map, nb)
         else:
             rawf = raw.float().cpu().numpy()
+            if self.bounds is not None:
+                bnd = self.bounds.numpy()[list(chan_map)]   # (CIN, 2)
+                lo, hi = bnd[None, :, 0, None], bnd[None, :, 1, None]
             for j in range(nb):
                 seg = rawf[:, :, j * self.bucket_len:(j + 1) * self.bucket_len]
                 ok = ~np.isnan(seg)
+                if self.bounds is not None:
+                    acc = (lo <= seg) & (seg <= hi)     # False for NaN
+                    nrej = (ok & ~acc).sum(-1)          # (S, CIN)
+                    for ci, c in enumerate(chan_map):
+                        self.rej[:, c] += torch.from_numpy(nrej[:, ci])
+                    ok = acc
                 g = (self.head + j) % self.G
                 for ci, c in enumerate(chan_map):
                     self.bsum[:, c, g] = torch.from_numpy(
@@ -250,11 +302,17 @@ class StreamEngine:
             ci = chan_idx.to(torch.int32).contiguous().to(self.device)
             bi = bucket_d.contiguous()
             vi = vals.float().contiguous().to(self.device)
-            hip.check(hip.load(hip.PREPROC).tskd_preproc_ingest_events(
-                hip.ptr(si), hip.ptr(ci), hip.ptr(bi), hip.ptr(vi),
-                hip.ptr(self.bsum), hip.ptr(self.bcnt), self.C, self.G,
-                len(vi), min_bucket, self._bst, hip.stream_ptr()),
-                "tskd_preproc_ingest_events")
+            lib = hip.load(hip.PREPROC)
+            args = (hip.ptr(si), hip.ptr(ci), hip.ptr(bi), hip.ptr(vi),
+                    hip.ptr(self.bsum), hip.ptr(self.bcnt), self.C, self.G,
+                    len(vi), min_bucket, self._bst)
+            if self.bounds is None:
+                hip.check(lib.tskd_preproc_ingest_events(
+                    *args, hip.stream_ptr()), "tskd_preproc_ingest_events")
+            else:
+                hip.check(lib.tskd_preproc_ingest_events_gated(
+                    *args, hip.ptr(self.bounds), hip.ptr(self.rej),
+                    hip.stream_ptr()), "tskd_preproc_ingest_events_gated")
             if advance_to is None and len(tsd):
                 advance_to = float(tsd.max().item())
         else:
@@ -267,6 +325,17 @@ class StreamEngine:
             self._clear_ahead(int(bucket.max().item()) + 1 if len(bucket)
                               else 0)
             ok = (~torch.isnan(vals)) & (bucket >= min_bucket)
+            if self.bounds is not None:
+                # late drop first: a late event is not counted as rejected
+                v32 = vals.float()
+                bnd = self.bounds[chan_idx.long()]
+                acc = (bnd[:, 0] <= v32) & (v32 <= bnd[:, 1])
+                out = ok & ~acc
+                if out.any():
+                    np.add.at(self.rej.numpy().reshape(-1),
+                              stream_idx[out].numpy() * self.C
+                              + chan_idx[out].numpy(), 1)
+                ok = ok & acc
             if ok.any():
                 flat = ((stream_idx[ok].numpy() * self.C
                          + chan_idx[ok].numpy()) * self.G
@@ -701,6 +770,24 @@ class StreamEngine:
             self.bcnt[idx] = 0
             self.proc[idx] = 0
             self.last_val[idx] = float("nan")
+        if self.rej is not None:
+            self.rej[torch.from_numpy(ids).to(self.device)] = 0
+
+    def rejected(self, sids=None) -> torch.Tensor:
+        """Samples the signal-quality gate rejected since the engine began
+        (or since the slot's last ``reset_streams``): int64 ``(n, C)`` per
+        listed stream (all S when ``sids`` is None) and wire channel, on the
+        engine's device. Rows follow the list order, duplicates are
+        harmless. NaN samples and late events are not in it. The counter is
+        not part of a snapshot: a restored engine counts from 0. ValueError:
+        an engine built without ``valid_range``, or an id outside [0, S)."""
+        if self.rej is None:
+            raise ValueError("this engine has no signal-quality gate "
+                             "(built without valid_range)")
+        if sids is None:
+            return self.rej.clone()
+        ids = self._check_sids(sids)
+        return self.rej[torch.from_numpy(ids).to(self.device)]
 
     def admit(self, sids, at=None) -> None:
         """A new occupant takes the listed slots now: ``stream_ready`` for

@@ -17,6 +17,9 @@ from typing import Dict, Optional
 
 STREAM_STATES = ("active", "admitted_total", "evicted_total",
                  "rejected_total",
+                 # signal-quality gate (serve --valid-range): samples outside
+                 # their channel's plausibility bounds, dropped at ingest
+                 "rejected_samples_total",
                  # warm restart: state files refused at start (cold starts)
                  "restore_failed",
                  # coverage gate (serve --min-coverage): predictions withheld
@@ -44,6 +47,9 @@ class StageTimer:
         # optional stream-lifecycle gauges/counters of this stage: any of
         # "active", "admitted_total", "evicted_total", "rejected_total"
         self.gauges: Dict[str, float] = dict(gauges or {})
+        # signal-quality gate: samples rejected at ingest since start, by
+        # channel name (empty unless the stage runs a gate)
+        self.rejected_samples: Dict[str, int] = {}
         self.lat = deque(maxlen=window)
         self.items = 0
         self.calls = 0
@@ -81,6 +87,8 @@ class StageTimer:
         }
         if self.gauges:
             snap["streams"] = dict(self.gauges)
+        if self.rejected_samples:
+            snap["rejected_samples"] = dict(self.rejected_samples)
         return snap
 
     def log_line(self) -> str:
@@ -137,4 +145,13 @@ def prometheus_text(timers) -> str:
                 v = int(v) if float(v).is_integer() else float(v)
                 lines.append(f'tskd_streams{{stage="{t.name}",'
                              f'state="{state}"}} {v}')
+    gated = [t for t in timers if getattr(t, "rejected_samples", None)]
+    if gated:
+        lines.append("# HELP tskd_rejected_samples_total Samples outside "
+                     "their channel's plausibility bounds, dropped at ingest.")
+        lines.append("# TYPE tskd_rejected_samples_total counter")
+    for t in gated:
+        for channel, v in t.rejected_samples.items():
+            lines.append(f'tskd_rejected_samples_total{{stage="{t.name}",'
+                         f'channel="{channel}"}} {int(v)}')
     return "\n".join(lines) + "\n"

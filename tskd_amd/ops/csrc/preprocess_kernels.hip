@@ -9,6 +9,8 @@
 //      Dense path: one wavefront per bucket, coalesced strided loads +
 //      wave shuffle reduction. Sparse path (irregular event batches, the
 //      real numerics records at fs=1/60 Hz): atomicAdd into buckets.
+//      Both have a GATED instantiation (signal-quality gate): per-channel
+//      plausibility bounds, rejected samples counted into rej (S, C) int64.
 //
 //   2. window_fill: the Spark groupBy(key, channel, window(180 s, 5 s))
 //      .agg(avg) — a window STARTING at grid g covers buckets [g, g+36) and
@@ -65,7 +67,46 @@ typedef float f32x2p_ __attribute__((ext_vector_type(2)));
 // busy (78/16 = 4.9 balanced iterations per group).
 #define ING_GRP 4   // buckets per wave
 #define ING_GL 16   // lanes per bucket group
-template <class DT>
+
+// One sample into a lane's accumulators. Ungated: present iff not NaN.
+// GATED (signal-quality gate, docs/PARITY.md divergence 15): accepted iff
+// lo <= f <= hi in fp32 — false for NaN, and with infinite bounds true for
+// exactly the samples !isnan accepts, ±inf included. A sample that is
+// neither accepted nor NaN is rejected: it reaches neither sum nor cnt and
+// adds 1 to rej.
+template <bool GATED>
+__device__ __forceinline__ void ingest_acc(float f, float lo, float hi,
+                                           float& sum, float& cnt, int& rej) {
+    if constexpr (GATED) {
+        // selects, not branches: a rejected sample adds +0 (sum never
+        // holds -0, so that leaves it bit for bit alone) and the kernel
+        // stays straight-line code
+        const bool acc = (lo <= f) & (f <= hi);
+        sum += acc ? f : 0.f;
+        cnt += acc ? 1.f : 0.f;
+        rej += (int)(!acc & !isnan(f));
+    } else {
+        if (!isnan(f)) { sum += f; cnt += 1.f; }
+    }
+}
+
+// Both dense kernels. The gate's two arguments travel as a parameter pack
+// (empty when !GATED), so the ungated instantiation keeps the argument list
+// and the code it had before the gate existed. GATED adds: the row's bounds
+// (by wire channel, wave-uniform: a wave's four buckets share one (s, cin)
+// row) loaded once per task, a third per-lane accumulator reduced over the
+// wave (its four bucket groups count into the same rej[s, c]), and ONE 64-bit
+// atomicAdd per task into rej[s, c], issued by lane 0 and only when the wave
+// rejected something — a clean stream costs no atomics. Every mask that
+// keeps a sample out of sum/cnt (boundary chunks, the tensor-final scalar
+// tail) keeps it out of rej: all three go through ingest_acc.
+__device__ __forceinline__ const float* gate_bounds(const float* b,
+                                                    long long*) { return b; }
+__device__ __forceinline__ long long* gate_rej(const float*, long long* r) {
+    return r;
+}
+
+template <class DT, bool GATED, class... GA>
 __global__ void ingest_dense_kernel(
     const DT* __restrict__ raw,     // (S, CIN, T)
     float* __restrict__ bsum,       // (S, C, G), element stride BST
@@ -73,7 +114,8 @@ __global__ void ingest_dense_kernel(
     const int* __restrict__ chan_map,  // (CIN) raw row -> wire channel
     int S, int CIN, int C, int T, int G,
     int bucket_len, long head_in,   // buckets written at [head, head+NB)
-    const long long* __restrict__ dstate, int BST)
+    const long long* __restrict__ dstate, int BST,
+    GA... gate)  // GATED: const float* bounds (C, 2), long long* rej (S, C)
 {
     const long head = ring_head(dstate, head_in);
     const int head_mod = (int)(head % G);  // hoisted: no 64-bit mod per task
@@ -98,6 +140,16 @@ __global__ void ingest_dense_kernel(
         const DT* src = raw + ((long)s * CIN + cin) * T +
                         (long)(active ? b : 0) * bucket_len;
         float sum = 0.f, cnt = 0.f;
+        float lo = 0.f, hi = 0.f;
+        int rej = 0, cg = 0;
+        if constexpr (GATED) {
+            // the row is the wave's: say so, and channel and bounds come
+            // through the scalar cache into scalar registers
+            const float* bounds = gate_bounds(gate...);
+            cg = chan_map[__builtin_amdgcn_readfirstlane(cin)];
+            lo = bounds[2 * cg];
+            hi = bounds[2 * cg + 1];
+        }
         // 16B-aligned vector body (bucket offsets like 625 samples are not
         // 16B-aligned): bf16 masks the boundary chunks, fp32 peels them.
         if (active) {
@@ -140,7 +192,7 @@ __global__ void ingest_dense_kernel(
                             #pragma unroll
                             for (int j = 0; j < 8; ++j) {
                                 const float f = bf16_to_f32(v[u].h[j]);
-                                if (!isnan(f)) { sum += f; cnt += 1.f; }
+                                ingest_acc<GATED>(f, lo, hi, sum, cnt, rej);
                             }
                         } else {  // boundary chunk: mask by sample index
                             #pragma unroll
@@ -148,7 +200,8 @@ __global__ void ingest_dense_kernel(
                                 const unsigned k = (unsigned)(idx0 + j);
                                 if (k < (unsigned)bucket_len) {
                                     const float f = bf16_to_f32(v[u].h[j]);
-                                    if (!isnan(f)) { sum += f; cnt += 1.f; }
+                                    ingest_acc<GATED>(f, lo, hi, sum, cnt,
+                                                      rej);
                                 }
                             }
                         }
@@ -159,14 +212,14 @@ __global__ void ingest_dense_kernel(
                          i < bucket_len;
                          i += ING_GL) {  // tensor-final bucket only
                         const float f = bf16_to_f32(su[i]);
-                        if (!isnan(f)) { sum += f; cnt += 1.f; }
+                        ingest_acc<GATED>(f, lo, hi, sum, cnt, rej);
                     }
             } else {
                 int pre = (int)(((16 - ((size_t)src & 15)) & 15) / 4);
                 if (pre > bucket_len) pre = bucket_len;
                 for (int i = lane; i < pre; i += ING_GL) {
                     const float f = (float)src[i];
-                    if (!isnan(f)) { sum += f; cnt += 1.f; }
+                    ingest_acc<GATED>(f, lo, hi, sum, cnt, rej);
                 }
                 const int quad = (bucket_len - pre) / 4;
                 const f32x4_* vp = (const f32x4_*)((const float*)src + pre);
@@ -181,16 +234,16 @@ __global__ void ingest_dense_kernel(
                     #pragma unroll
                     for (int u = 0; u < 5; ++u) {
                         if (base + u * ING_GL < quad) {
-                            if (!isnan(v[u].x)) { sum += v[u].x; cnt += 1.f; }
-                            if (!isnan(v[u].y)) { sum += v[u].y; cnt += 1.f; }
-                            if (!isnan(v[u].z)) { sum += v[u].z; cnt += 1.f; }
-                            if (!isnan(v[u].w)) { sum += v[u].w; cnt += 1.f; }
+                            ingest_acc<GATED>(v[u].x, lo, hi, sum, cnt, rej);
+                            ingest_acc<GATED>(v[u].y, lo, hi, sum, cnt, rej);
+                            ingest_acc<GATED>(v[u].z, lo, hi, sum, cnt, rej);
+                            ingest_acc<GATED>(v[u].w, lo, hi, sum, cnt, rej);
                         }
                     }
                 }
                 for (int i = pre + quad * 4 + lane; i < bucket_len; i += ING_GL) {
                     const float f = (float)src[i];
-                    if (!isnan(f)) { sum += f; cnt += 1.f; }
+                    ingest_acc<GATED>(f, lo, hi, sum, cnt, rej);
                 }
             }
         }
@@ -208,17 +261,33 @@ __global__ void ingest_dense_kernel(
             bsum[idx] = sum;
             bcnt[idx] = cnt;
         }
+        if constexpr (GATED) {
+            // the wave's four groups count into the same rej[s, c]
+            // (inactive groups hold 0): reduce over the whole wave
+            #pragma unroll
+            for (int off = WAVE / 2; off > 0; off >>= 1)
+                rej += __shfl_xor(rej, off);
+            if (wlane == 0 && rej > 0)
+                atomicAdd((unsigned long long*)gate_rej(gate...)
+                              + ((long)s * C + cg),
+                          (unsigned long long)rej);
+        }
     }
 }
 
 // ---------------------------------------------------------------------------
 // 1b. Sparse ingest: event tuples (stream, chan, grid_bucket, value)
 // ---------------------------------------------------------------------------
+// GATED: late drop first (a late event is never counted as rejected), then
+// the channel's bounds: one extra compare, and one extra 64-bit atomic on the
+// rare rejected event.
+template <bool GATED, class... GA>
 __global__ void ingest_events_kernel(
     const int* __restrict__ ev_stream, const int* __restrict__ ev_chan,
     const long* __restrict__ ev_bucket, const float* __restrict__ ev_val,
     float* __restrict__ bsum, float* __restrict__ bcnt,
-    int C, int G, long n_events, long min_bucket, int BST)
+    int C, int G, long n_events, long min_bucket, int BST,
+    GA... gate)  // GATED: const float* bounds (C, 2), long long* rej (S, C)
 {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_events;
          i += (long)gridDim.x * blockDim.x) {
@@ -226,6 +295,15 @@ __global__ void ingest_events_kernel(
         if (b < min_bucket) continue;  // behind the watermark: dropped (late data)
         const float v = ev_val[i];
         if (isnan(v)) continue;
+        if constexpr (GATED) {
+            const float* bounds = gate_bounds(gate...);
+            const int c = ev_chan[i];
+            if (!(bounds[2 * c] <= v && v <= bounds[2 * c + 1])) {
+                atomicAdd((unsigned long long*)gate_rej(gate...)
+                              + ((long)ev_stream[i] * C + c), 1ull);
+                continue;
+            }
+        }
         const long idx = (((long)ev_stream[i] * C + ev_chan[i]) * G
                           + b % G) * BST;
         atomicAdd(&bsum[idx], v);
@@ -930,13 +1008,14 @@ static inline int grid_for(long n, int block) {
 
 extern "C" {
 
-int tskd_preproc_ingest_dense(const void* raw, int raw_is_bf16,
-                              float* bsum, float* bcnt, const int* chan_map,
-                              int S, int CIN, int C, int T, int G,
-                              int bucket_len, long head,
-                              const long long* dstate, int bst,
-                              void* stream) {
-    hipStream_t st = (hipStream_t)stream;
+// Shared launcher of the two dense entry points: bounds == null launches the
+// ungated kernels with their own (unchanged) argument list.
+static int launch_ingest_dense(const void* raw, int raw_is_bf16, float* bsum,
+                               float* bcnt, const int* chan_map, int S,
+                               int CIN, int C, int T, int G, int bucket_len,
+                               long head, const long long* dstate, int bst,
+                               const float* bounds, long long* rej,
+                               hipStream_t st) {
     const int NB = T / bucket_len;
     if (NB <= 0 || S <= 0) return 0;
     const long nwaves = (long)S * CIN * ((NB + ING_GRP - 1) / ING_GRP);
@@ -952,17 +1031,57 @@ int tskd_preproc_ingest_dense(const void* raw, int raw_is_bf16,
     const int grid = (int)blocks;
     // bf16: 5-deep load ILP with masked boundary chunks (no scalar peel);
     // fp32: 5-deep load ILP with a scalar head/tail peel.
-    if (raw_is_bf16)
-        hipLaunchKernelGGL((ingest_dense_kernel<unsigned short>), dim3(grid),
-                           dim3(256), 0, st, (const unsigned short*)raw, bsum,
-                           bcnt, chan_map, S, CIN, C, T, G, bucket_len, head,
-                           dstate, bst);
+    if (bounds && raw_is_bf16)
+        hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, true,
+                                                const float*, long long*>),
+                           dim3(grid), dim3(256), 0, st,
+                           (const unsigned short*)raw, bsum, bcnt, chan_map,
+                           S, CIN, C, T, G, bucket_len, head, dstate, bst,
+                           bounds, rej);
+    else if (bounds)
+        hipLaunchKernelGGL((ingest_dense_kernel<float, true, const float*,
+                                                long long*>), dim3(grid),
+                           dim3(256), 0, st, (const float*)raw, bsum, bcnt,
+                           chan_map, S, CIN, C, T, G, bucket_len, head, dstate,
+                           bst, bounds, rej);
+    else if (raw_is_bf16)
+        hipLaunchKernelGGL((ingest_dense_kernel<unsigned short, false>),
+                           dim3(grid), dim3(256), 0, st,
+                           (const unsigned short*)raw, bsum, bcnt, chan_map,
+                           S, CIN, C, T, G, bucket_len, head, dstate, bst);
     else
-        hipLaunchKernelGGL((ingest_dense_kernel<float>), dim3(grid),
+        hipLaunchKernelGGL((ingest_dense_kernel<float, false>), dim3(grid),
                            dim3(256), 0, st, (const float*)raw, bsum, bcnt,
                            chan_map, S, CIN, C, T, G, bucket_len, head, dstate,
                            bst);
     return (int)hipGetLastError();
+}
+
+int tskd_preproc_ingest_dense(const void* raw, int raw_is_bf16,
+                              float* bsum, float* bcnt, const int* chan_map,
+                              int S, int CIN, int C, int T, int G,
+                              int bucket_len, long head,
+                              const long long* dstate, int bst,
+                              void* stream) {
+    return launch_ingest_dense(raw, raw_is_bf16, bsum, bcnt, chan_map, S, CIN,
+                               C, T, G, bucket_len, head, dstate, bst, nullptr,
+                               nullptr, (hipStream_t)stream);
+}
+
+// Signal-quality gate: the same launch with per-wire-channel bounds (C, 2)
+// fp32 [lo, hi] and the cumulative (S, C) int64 rejected counter. -4: a null
+// bounds or counter pointer.
+int tskd_preproc_ingest_dense_gated(const void* raw, int raw_is_bf16,
+                                    float* bsum, float* bcnt,
+                                    const int* chan_map, int S, int CIN,
+                                    int C, int T, int G, int bucket_len,
+                                    long head, const long long* dstate,
+                                    int bst, const float* bounds,
+                                    long long* rej, void* stream) {
+    if (!bounds || !rej) return -4;
+    return launch_ingest_dense(raw, raw_is_bf16, bsum, bcnt, chan_map, S, CIN,
+                               C, T, G, bucket_len, head, dstate, bst, bounds,
+                               rej, (hipStream_t)stream);
 }
 
 int tskd_preproc_ingest_events(const int* ev_stream, const int* ev_chan,
@@ -971,10 +1090,28 @@ int tskd_preproc_ingest_events(const int* ev_stream, const int* ev_chan,
                                long n_events, long min_bucket, int bst,
                                void* stream) {
     if (n_events <= 0) return 0;
-    hipLaunchKernelGGL(ingest_events_kernel, dim3(grid_for(n_events, 256)),
-                       dim3(256), 0, (hipStream_t)stream, ev_stream, ev_chan,
-                       ev_bucket, ev_val, bsum, bcnt, C, G, n_events,
-                       min_bucket, bst);
+    hipLaunchKernelGGL((ingest_events_kernel<false>),
+                       dim3(grid_for(n_events, 256)), dim3(256), 0,
+                       (hipStream_t)stream, ev_stream, ev_chan, ev_bucket,
+                       ev_val, bsum, bcnt, C, G, n_events, min_bucket, bst);
+    return (int)hipGetLastError();
+}
+
+int tskd_preproc_ingest_events_gated(const int* ev_stream, const int* ev_chan,
+                                     const long* ev_bucket,
+                                     const float* ev_val, float* bsum,
+                                     float* bcnt, int C, int G, long n_events,
+                                     long min_bucket, int bst,
+                                     const float* bounds, long long* rej,
+                                     void* stream) {
+    if (!bounds || !rej) return -4;
+    if (n_events <= 0) return 0;
+    hipLaunchKernelGGL((ingest_events_kernel<true, const float*,
+                                             long long*>),
+                       dim3(grid_for(n_events, 256)), dim3(256), 0,
+                       (hipStream_t)stream, ev_stream, ev_chan, ev_bucket,
+                       ev_val, bsum, bcnt, C, G, n_events, min_bucket, bst,
+                       bounds, rej);
     return (int)hipGetLastError();
 }
 

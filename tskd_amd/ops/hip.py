@@ -38,7 +38,11 @@ SIGNATURES = {
     PREPROC: {
         "tskd_preproc_ingest_dense": [P, I, P, P, P, I, I, I, I, I, I, L, P,
                                       I, P],
+        "tskd_preproc_ingest_dense_gated": [P, I, P, P, P, I, I, I, I, I, I,
+                                            L, P, I, P, P, P],
         "tskd_preproc_ingest_events": [P, P, P, P, P, P, I, I, L, L, I, P],
+        "tskd_preproc_ingest_events_gated": [P, P, P, P, P, P, I, I, L, L, I,
+                                             P, P, P],
         "tskd_preproc_clear_buckets": [P, P, I, I, I, L, I, I, P],
         "tskd_preproc_reset_streams": [P, I, P, P, P, P, I, I, I, I, P],
         "tskd_preproc_snapshot_streams": [P, I, P, P, P, P, I, I, I, I, L, I,

@@ -27,10 +27,18 @@ def record_to_training_frame(p_signal: np.ndarray, fs: float,
                              sig_names: Sequence[str],
                              channel_names: Sequence[str],
                              start_s: float = 0.0,
-                             ca_time_s: Optional[float] = None) -> pd.DataFrame:
+                             ca_time_s: Optional[float] = None,
+                             valid_range=None) -> pd.DataFrame:
     """Reference get_record_df (explore_torch.ipynb cell 2): to 5-s grid via
     resample().first(), rolling('3min').mean(), interpolate(linear); columns
-    ordered by the configured channel list with missing channels = 0."""
+    ordered by the configured channel list with missing channels = 0.
+
+    ``valid_range``: the serving gate's bounds (docs/PARITY.md divergence
+    15), one ``(lo, hi)`` per entry of ``channel_names`` with None = open.
+    A sample of the record outside its channel's closed interval, compared
+    in fp32 as the ingest kernels compare it, becomes NaN before the 5-s
+    resample, so a model can be trained on what a gated daemon serves.
+    None (the default) changes nothing."""
     n = p_signal.shape[0]
     idx = pd.to_timedelta(np.arange(n) / fs, unit="s")
     df = pd.DataFrame(p_signal, index=idx, columns=list(sig_names))
@@ -44,6 +52,14 @@ def record_to_training_frame(p_signal: np.ndarray, fs: float,
         if c not in df.columns:
             df[c] = 0.0
     df = df[list(channel_names)]
+    if valid_range is not None:
+        from tskd_amd.engine.stream_engine import check_valid_range
+        bnd = check_valid_range(valid_range, len(channel_names))
+        v = df.values.astype(np.float32)
+        bad = ~((bnd[:, 0] <= v) & (v <= bnd[:, 1])) & ~np.isnan(v)
+        # a configured channel the record lacks is the constant 0 column
+        bad[:, [c not in sig_names for c in channel_names]] = False
+        df = df.mask(bad)
     df = df.resample("5s").first()
     df = df.rolling("3min").mean()
     df = df.interpolate(method="linear")
