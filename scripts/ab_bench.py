@@ -9,7 +9,13 @@ time (e.g. TSKD_CONVBWD_GRID), so they can flip per round without reload.
 Usage:
   python scripts/ab_bench.py --mode train --knob TSKD_CONVBWD_GRID \
       --a 2048 --b 8192 --rounds 8 --steps 8
-Reports per-variant median/min step time and the median delta.
+Reports per-variant median/min step time, each arm's round spread and the
+median delta.
+
+Two BUILDS of the inference kernel library (e.g. the parent commit's and the
+working tree's) are compared the same way: --knob lib:mycnn with --a/--b the
+paths of the two .so files; the arm's build is swapped into the binding
+cache per round.
 """
 
 import argparse
@@ -88,10 +94,19 @@ def main() -> None:
         step()
     torch.cuda.synchronize()
 
+    from tskd_amd.ops import hip
+    libs = {}
+    if args.knob == "lib:mycnn":
+        libs = {v: hip.open_lib(hip.MYCNN, os.path.abspath(v))
+                for v in (args.a, args.b)}
+
     times = {"A": [], "B": []}
     for r in range(args.rounds):
         for tag, val in (("A", args.a), ("B", args.b)):
-            os.environ[args.knob] = str(val)
+            if libs:
+                hip.use_lib(hip.MYCNN, libs[val])
+            else:
+                os.environ[args.knob] = str(val)
             step()  # one unmeasured step after the knob flip
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -104,6 +119,11 @@ def main() -> None:
           f"min {min(times['A'])*1e3:.4f} ms")
     print(f"B ({args.knob}={args.b}): median {mb*1e3:.4f} ms  "
           f"min {min(times['B'])*1e3:.4f} ms")
+    for tag in ("A", "B"):
+        t = times[tag]
+        print(f"{tag} rounds (ms): " + " ".join(f"{v*1e3:.4f}" for v in t)
+              + f"  spread (max-min)/median "
+              f"{(max(t)-min(t))/statistics.median(t)*100:.2f}%")
     print(f"delta (B vs A): {(mb/ma-1)*100:+.2f}% median  "
           f"[rounds={args.rounds}, steps={args.steps}]")
 

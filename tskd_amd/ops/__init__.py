@@ -35,7 +35,9 @@ def _age_ptr(age: Optional[torch.Tensor], s: int, n: int) -> Tuple:
     return hip.ptr(age), age
 
 
-TLAST_SLACK = 256  # trailing elements the timelast conv kernel may overread
+# trailing elements the timelast conv kernel may overread: they must be
+# addressable, their contents never reach a result
+TLAST_SLACK = 256
 
 # channel-attribution baselines -> OCCLUDE_* in csrc/mycnn_kernels.hip
 BASELINES = {"hold": 0, "zero": 1}
@@ -93,6 +95,8 @@ class MyCNNEngine:
         counts, bf16); its fragment reads may overrun the tensor by up to
         TLAST_SLACK elements, so non-slack-tagged inputs are copied into a
         padded buffer (allocate with :func:`alloc_windows` to avoid that).
+        What the overrun reads, the slack or the next window, reaches no
+        result: the kernel clears those fragment words.
         """
         timelast = (x.shape[-1] == self.cin and x.shape[-2] == 120
                     and self.cin != 120)

@@ -303,9 +303,17 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_kernel(
 // keeps LDS only for the small pooled tail.
 //
 // NOTE: fragment reads overrun a window by up to (KSTEPS*32 - KK + C1%16
-// rows) elements into the NEXT window (zero B-columns make the values
-// irrelevant); callers must allocate the x buffer with TLAST_SLACK trailing
-// elements (tskd_amd/ops wrapper does).
+// rows) elements into the NEXT window; callers must allocate the x buffer
+// with TLAST_SLACK trailing elements (tskd_amd/ops wrapper does). Only the
+// last M-tile reaches that far, and only at reduction indices kk >= KK, where
+// the B rows are zero. A zero B row does not discard a NaN or an Inf
+// (0 x NaN = NaN), so the last tile clears those A half-words first: the
+// next window's (or the slack's) contents never reach a conv1 row. A finite
+// value cleared this way contributed +-0 to an accumulator that starts at
+// +0 and is never -0, so finite inputs give the same bits as without it.
+// The mask also clears the window's OWN kk >= KK words, in the last tile
+// only: a non-finite value late in a window still turns that window's rows
+// of the earlier tiles into NaN (same patient's score; docs/PARITY.md).
 // ---------------------------------------------------------------------------
 #define TLAST_SLACK 256  // trailing bf16 elements required after the tensor
 template <class G>
@@ -333,6 +341,19 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_tlast_kernel(
     // per-lane fragment base within a window (dwords): rows l&15, k-group l>>4
     const int lane_dw = ((lane & 15) * G::CIN + (lane >> 4) * 8) / 2;
     __shared__ float lds_c1b[WG_WAVES][4 * G::C1];  // 2nd window of the pair
+    // Last-tile A masks for the k-steps that reach past KK: dword q of step
+    // st holds kk = st*32 + (lane>>4)*8 + 2q and kk + 1.
+    constexpr int ST0 = G::KK / 32;   // first k-step with a kk >= KK
+    unsigned int kmask[G::KSTEPS - ST0 > 0 ? G::KSTEPS - ST0 : 1][4];
+    #pragma unroll
+    for (int st = ST0; st < G::KSTEPS; ++st) {
+        #pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int kk = st * 32 + (lane >> 4) * 8 + 2 * q;
+            kmask[st - ST0][q] = (kk < G::KK ? 0x0000ffffu : 0u)
+                               | (kk + 1 < G::KK ? 0xffff0000u : 0u);
+        }
+    }
 
     // TWO windows per wave: the pair's MFMA/load chains are independent, so
     // the in-order wave covers one chain's global-load latency with the
@@ -365,6 +386,13 @@ __global__ __launch_bounds__(WG_THREADS) void conv_stack_mfma_tlast_kernel(
                 ab.d[1] = baseb[st * 16 + 1];
                 ab.d[2] = baseb[st * 16 + 2];
                 ab.d[3] = baseb[st * 16 + 3];
+                if (st >= ST0 && mt == G::MTILES - 1) {   // uniform
+                    #pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        aa.d[q] &= kmask[st - ST0][q];
+                        ab.d[q] &= kmask[st - ST0][q];
+                    }
+                }
                 acca = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aa.v, bfr[st],
                                                                acca, 0, 0, 0);
                 accb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab.v, bfr[st],

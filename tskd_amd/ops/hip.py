@@ -86,12 +86,25 @@ def load(name: str) -> ctypes.CDLL:
                 _build.build(name)
             except Exception as e:
                 raise RuntimeError(f"hipcc build failed: {e}") from e
-        lib = ctypes.CDLL(path)
-        for fn, argtypes in SIGNATURES[name].items():
-            entry = getattr(lib, fn)
-            entry.restype = I
-            entry.argtypes = argtypes
-        _libs[name] = lib
+        lib = _libs[name] = open_lib(name, path)
+    return lib
+
+
+def use_lib(name: str, lib: ctypes.CDLL) -> None:
+    """Make ``lib`` (from :func:`open_lib`) what :func:`load` returns for
+    ``name`` from now on: scripts/ab_bench.py times two builds of a library
+    against each other by swapping them per round."""
+    _libs[name] = lib
+
+
+def open_lib(name: str, path: str) -> ctypes.CDLL:
+    """The build of library ``name`` at ``path`` with every table entry
+    typed; not cached (see :func:`use_lib`)."""
+    lib = ctypes.CDLL(path)
+    for fn, argtypes in SIGNATURES[name].items():
+        entry = getattr(lib, fn)
+        entry.restype = I
+        entry.argtypes = argtypes
     return lib
 
 
